@@ -6,7 +6,9 @@ One "step" = one pass of the hot path over one batch of synthetic walkers per GP
     3 doubles (the <E_L> site of vqmc.py:196).
 Walkers shard over ranks with no exchange of coordinates (weak scaling, B per GPU fixed).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`.  A plain run sets up, warms up, times the steps and
+prints the line; `--full` adds what takes runs of its own (the sustained-clock kernel time, `cpu_baseline`, the legs of the other
+configurations).  `--dump-outputs DIR` writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -324,6 +326,21 @@ def walkers(B, seed):
     return torch.sort(x, dim=-1).values.contiguous()
 
 
+DUMP_MAX_VALUES = 1 << 23   # float32 values of log_pdf written by --dump-outputs over all ranks: 32 MB
+
+
+def dump_outputs(out_dir, lp, sums, rank, world):
+    """--dump-outputs: log_pdf of the last timed step (a fixed, seeded sample of it beyond DUMP_MAX_VALUES / world values) and its block sums."""
+    os.makedirs(out_dir, exist_ok=True)
+    v = lp.cpu().numpy().astype(np.float32)
+    cap = DUMP_MAX_VALUES // world
+    if v.size > cap:
+        v = v[np.sort(np.random.default_rng(0).choice(v.size, cap, replace=False))]
+    np.save(os.path.join(out_dir, "log_pdf.npy" if world == 1 else f"log_pdf_rank{rank}.npy"), v)
+    if rank == 0:
+        np.save(os.path.join(out_dir, "block_sums.npy"), sums.cpu().numpy().astype(np.float64))
+
+
 def host_cores():
     """Cores this process may really use: the affinity mask capped by the cgroup CPU quota."""
     return cpu_share()
@@ -391,12 +408,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--batch", type=int, default=1 << 20, help="walkers per GPU")
     ap.add_argument("--kernel", default="auto", choices=["auto", "scalar", "mfma", "wave"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (33-knot variant, batch 256, D = 8, 1-thread CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the measurements that take runs of their own: the sustained-clock kernel time, the CPU "
+                         "baselines and the secondary legs (off by default: a plain run does only what its headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the sustained-clock time and the secondary legs (33-knot variant, batch 256, D = 8, 1-thread CPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy: log_pdf of the walkers (float32, per rank when N > 1; "
+                         f"beyond {DUMP_MAX_VALUES} values over all ranks a fixed, seeded sample of them) and the step's block sums "
+                         "[sum, sum^2, n] (float64, all-reduced when N > 1)")
     ap.add_argument("--workload", default="he_logpdf", choices=["he_logpdf", "rqs", "vqmc", "nsc"],
                     help="he_logpdf: the BASELINE metric (default).  rqs: the RQS bijector kernel alone (SURVEY row a12), an "
                          "HBM-bound elementwise op: 2 dims x `--batch` walkers, 32 bins")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "he_logpdf":
+        raise SystemExit(f"--dump-outputs: only the he_logpdf workload writes its outputs, not {args.workload}")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args.gpus)       # before anything touches the GPU: the ranks are fresh child processes
     if args.workload == "rqs":
@@ -495,6 +522,8 @@ def main():
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     last = sums_all[(n_done[0] - 1) % sums_all.shape[0]]
     mean_logp = float((last[0] / last[2]).item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lp, last, rank, world)
     kern_ms_ranks, solo_rates = [kern_ms], None
     if use_dist:   # every rank's own kernel time, so that an N > 1 record can be checked against the N = 1 one
         # ... and its N = 1-style rate: the same K steps (kernel + block sums) WITHOUT the collective, all ranks at once (what a rank of a
@@ -511,9 +540,9 @@ def main():
         kern_ms_ranks = [float(g[0].item()) for g in gathered]
         solo_rates = [float(g[1].item()) for g in gathered]
     # AFTER the timed region (never part of `value`): the same launch once the device has reached its sustained clocks -- from an idle GPU
-    # the first ~60 back-to-back launches take 0.29 - 0.32 ms, from ~200 on 15 % less (scratch/time_warm.py)
+    # the first ~60 back-to-back launches take 0.29 - 0.32 ms, from ~200 on 15 % less (scratch/time_warm.py).  --full only, like every leg below
     sustained = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         n_before = max(0, 300 - args.steps - args.warmup)
         sustained = {"kernel_ms": kernel_ms(model, x, n=100, warm=n_before), "launches_before": n_before + args.steps + args.warmup + 1, "timed_launches": 100}
 
@@ -562,11 +591,11 @@ def main():
             out["scaling_efficiency"] = value / sum(solo_rates)
             out["roofline_per_rank"] = [{"kernel_ms": k, "achieved": B / (k * 1e-3) * MFMA_FLOP_PER_EVAL / 1e12, "unit": "TFLOP/s",
                                          "frac": B / (k * 1e-3) * MFMA_FLOP_PER_EVAL / 1e12 / PEAK_F16_MATRIX_TFLOPS} for k in kern_ms_ranks]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(flat, x_host.numpy())
             if not args.no_extras:
                 out["cpu_baseline_1thread"] = cpu_baseline_1thread(flat, x_host.numpy())
-        if world == 1 and not args.no_extras and args.kernel in ("auto", "mfma"):
+        if world == 1 and args.full and not args.no_extras and args.kernel in ("auto", "mfma"):
             out.update(extra_legs(model, flat))
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -805,6 +805,36 @@ def test_bench_two_rank_path_on_a_shared_gpu():
     assert bad.returncode != 0 and "WORLD_SIZE=2" in (bad.stdout + bad.stderr)
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: K timed steps, ms_per_step the time of one, none of the --full legs in the
+    line, and DIR holds the last step's log_pdf (the library's log_pdf of the same seeded walkers, bit for bit) and its block sums."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "65536", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "evals/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 65536 * 7 / (d["ms_per_step"] * 7e-3)) < 1e-6 * d["value"]
+    assert not {"kernel_ms_sustained", "cpu_baseline", "cpu_baseline_1thread", "variant_33knot", "loss_grad_2pow17"} & set(d)
+    assert sorted(os.listdir(out)) == ["block_sums.npy", "log_pdf.npy"]
+    lp, sums = np.load(out / "log_pdf.npy"), np.load(out / "block_sums.npy")
+    assert lp.dtype == np.float32 and lp.shape == (65536,) and sums.dtype == np.float64 and sums.shape == (3,)
+    model, _ = bench.he_model("auto")
+    assert np.array_equal(lp, model.log_pdf(bench.walkers(65536, 1234).cuda()).cpu().numpy())
+    assert sums[2] == 65536 and abs(sums[0] - lp.astype(np.float64).sum()) < 1e-9 * np.abs(lp).sum()
+    assert abs(sums[0] / sums[2] - d["config"]["mean_logp"]) < 1e-12 * abs(d["config"]["mean_logp"])
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_gated_conditioner_heads(kernel):
     """set_nn_output_grad_to_zero=True (model_factory.py:64-67; tests/test_boundary_constraints.py:30-31 builds get_model with it):

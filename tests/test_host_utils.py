@@ -1,4 +1,5 @@
-"""Host-side helpers that need no GPU: the inversion count of coordinates.py:41-51, bench.py's PMC-summary reader and its rank bookkeeping."""
+"""Host-side helpers that need no GPU: the inversion count of coordinates.py:41-51, bench.py's PMC-summary reader, its output dump and its rank
+bookkeeping."""
 import json
 import os
 import subprocess
@@ -41,6 +42,27 @@ def test_bench_reads_the_traffic_from_the_committed_pmc_summary(tmp_path, monkey
     monkeypatch.setattr(bench, "PMC_SUMMARIES", ("profiles/missing.txt", "profiles/s.txt"))
     t = bench.pmc_traffic()
     assert t == {"bytes": 128 * 1024, "source": "profiles/s.txt", "fetch_kb": 100.0, "write_kb": 28.0}
+
+
+def test_bench_dump_outputs_writes_log_pdf_and_block_sums(tmp_path, monkeypatch):
+    """--dump-outputs: log_pdf as float32 (whole, or a fixed seeded sample of at most DUMP_MAX_VALUES / world values) and the block sums as float64."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    lp = torch.arange(100, dtype=torch.float32) * 0.5 - 7.0
+    sums = torch.tensor([lp.sum().item(), (lp.double() ** 2).sum().item(), 100.0], dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "one"), lp, sums, 0, 1)
+    got = np.load(tmp_path / "one" / "log_pdf.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, lp.numpy())
+    s = np.load(tmp_path / "one" / "block_sums.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, sums.numpy())
+    # above the cap: per rank DUMP_MAX_VALUES / world values, the same ones on every run, in walker order; only rank 0 writes the sums
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), lp, sums, 1, 2)
+    a, b = np.load(tmp_path / "a" / "log_pdf_rank1.npy"), np.load(tmp_path / "b" / "log_pdf_rank1.npy")
+    assert a.dtype == np.float32 and a.size == 16 and np.array_equal(a, b) and np.all(np.diff(a) > 0) and np.isin(a, lp.numpy()).all()
+    assert sorted(os.listdir(tmp_path / "a")) == ["log_pdf_rank1.npy"]
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
