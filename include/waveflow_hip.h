@@ -362,6 +362,57 @@ int wf_block_sums(const float* v_dev, int64_t B, double* out_dev, void* workspac
                   void* stream);
 int64_t wf_block_sums_workspace_bytes(int64_t B);
 
+/* -- spline closures (wf_kernels_spline.hip) ------------------------------------------------------------------------------------- */
+
+/* One spline family with its tables on the device: what ISpline_fun / MSpline_fun / BSpline_fun's init_fun(rng, k, n_internal_knots,
+ * ...) closes over (isplines_jax.py:84-131, msplines_jax.py:67-108, bsplines_jax.py:52-116) minus the random initial_params.  All
+ * arithmetic is fp32 in the reference's operation order (the order of its XLA dot products and sums is unspecified; ascending here). */
+typedef struct {
+    int32_t kind;               /* WF_SPLINE_I, WF_SPLINE_M or WF_SPLINE_B (evaluated on its orthogonalised tables) */
+    int32_t degree;             /* k */
+    int32_t n_internal_knots;
+    int32_t n_mesh;             /* n_mesh_points */
+    int32_t zero_border;        /* I and M only: the coefficients start at basis 1 and end one before the last (nc = n_bases - 2) */
+    wf_bc left, right;          /* constraints_dict_left / _right (I: a right {0: v} needs v == 1, isplines_jax.py:174-179) */
+} wf_spline_desc;
+
+typedef struct wf_spline wf_spline;
+
+/* Builds (tables_host == NULL: wf_tables_build) or uploads the fp64 tables, rounded once to fp32 as jnp.array(np.load(...)) does --
+ * how the reference's on-disk cache is honoured (isplines_jax.py:104-131, msplines_jax.py:84-108, bsplines_jax.py:68-116):
+ *   tables_host [4][n_bases][n_mesh]: the evaluated tables (kind B: the orthogonalised ones, cached_o_bases_dict);
+ *   aux_host    kind B only, required with tables_host: plain B tables [4][n_bases][n_mesh], then b_to_ob [n_bases][n_bases], then
+ *               ob_to_b [n_bases][n_bases]; ignored otherwise.
+ * n_bases > 64: WF_ERR_UNSUPPORTED.  No gfx950 device: WF_ERR_NO_DEVICE. */
+int wf_spline_create(const wf_spline_desc* desc, const double* tables_host, const double* aux_host, int device, wf_spline** out);
+void wf_spline_destroy(wf_spline* sp);
+int wf_spline_n_bases(const wf_spline* sp);
+
+/* apply_fun_vec / apply_fun_vec_grad (isplines_jax.py:139-150 -> ispline :69-80, I_cached :45-56, defjvp :59-66; msplines_jax.py:116-124;
+ * bsplines_jax.py:127-140): y[r] = sum_i c[r][i] * X(T[nd], base + i, x[r]) for c_dev [N][nc] (nc = n_bases - 2 zero_border), x_dev [N],
+ * the table lerp X_cached; dy_dev (may be NULL, nd <= 2) the same sum over T[nd + 1].  Kind B first maps c to
+ * p = normalised(c @ ob_to_b) and sums p against the orthogonalised tables, as the reference does. */
+int wf_spline_apply(const wf_spline* sp, const float* c_dev, int64_t N, const float* x_dev, int32_t nd, float* y_dev, float* dy_dev, void* stream);
+
+/* reverse_fun_vec of ISpline_fun (isplines_jax.py:152-156 -> utils/helpers.py:150-166): bisection on [0, 1] of apply(c[r], .) - y[r]
+ * with tolerance tol; x_dev [N] = the final `low`.  At most 200 halvings.  Kind I only (else WF_ERR_UNSUPPORTED). */
+int wf_spline_reverse(const wf_spline* sp, const float* c_dev, int64_t N, const float* y_dev, float tol, float* x_dev, void* stream);
+
+/* enforce_boundary_conditions (isplines_jax.py:158-194, msplines_jax.py:156-184, bsplines_jax.py:173-199) of w_dev [N][nw]
+ * (nw <= n_bases; the table rows are indexed with nw, not shifted by zero_border, as in the reference) -> out_dev [N][nw] (may equal
+ * w_dev); kind B reads the plain B tables.  Final division by sum(w) (I, M) or sqrt(sum(w^2)) (B). */
+int wf_spline_enforce_bc(const wf_spline* sp, const float* w_dev, int64_t N, int32_t nw, float* out_dev, void* stream);
+
+/* remove_bias (isplines_jax.py:196-202, msplines_jax.py:186-192) of p_dev [N][nw] -> out_dev [N][nw] (may equal p_dev).  Kinds I, M. */
+int wf_spline_remove_bias(const wf_spline* sp, const float* p_dev, int64_t N, int32_t nw, float* out_dev, void* stream);
+
+/* sample_fun_vec (msplines_jax.py:129-154, bsplines_jax.py:144-171): x_dev [N][num_samples] by rejection sampling under the reference's
+ * bound ymax (M: max(c) * len(knots); B: max((normalised(c @ ob_to_b) @ b_to_ob)^2)), so the density is proportional to min(f, ymax)
+ * (M) / min(f^2, ymax) (B).  Philox4x32-10 keyed by (seed, row, slot), not JAX's threefry (parity unpinned).  At most max_proposals
+ * proposals per slot: a slot that exhausts them is written as NaN.  Kinds M, B. */
+int wf_spline_sample(const wf_spline* sp, uint64_t seed, const float* c_dev, int64_t N, int32_t num_samples, int32_t max_proposals, float* x_dev,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,12 @@ class ModelDesc(ctypes.Structure):
                 ("nsc_bins", ctypes.c_int32), ("nsc_tail_bound", ctypes.c_float), ("nsc_hidden", ctypes.c_int32), ("nsc_reverse", ctypes.c_int32)]
 
 
+class SplineDesc(ctypes.Structure):
+    """wf_spline_desc (include/waveflow_hip.h)"""
+    _fields_ = [("kind", ctypes.c_int32), ("degree", ctypes.c_int32), ("n_internal_knots", ctypes.c_int32), ("n_mesh", ctypes.c_int32),
+                ("zero_border", ctypes.c_int32), ("left", BC), ("right", BC)]
+
+
 class TrainState(ctypes.Structure):
     """wf_train_state (include/waveflow_hip.h)"""
     _fields_ = [("params_dev", ctypes.c_void_p), ("m_dev", ctypes.c_void_p), ("v_dev", ctypes.c_void_p), ("counter_dev", ctypes.c_void_p),
@@ -71,7 +77,9 @@ EXPORTS = ["wf_abi_version", "wf_strerror", "wf_last_hip_error", "wf_last_hip_er
            "wf_psi_vjp", "wf_psi_vjp_workspace_bytes", "wf_vqmc_seeds",
            "wf_logpdf_vjp", "wf_logpdf_vjp_workspace_bytes", "wf_vqmc_loss_grad", "wf_model_set_params_device", "wf_adam_step",
            "wf_vqmc_train_step", "wf_vqmc_train_step_workspace_bytes", "wf_nsc_fwd", "wf_nsc_workspace_bytes", "wf_logpdf_loss_grad", "wf_mle_train_step", "wf_mle_train_step_workspace_bytes", "wf_vqmc_train_step_local",
-           "wf_vqmc_train_step_apply", "wf_psi_antisym_fwd", "wf_logpdf_unsorted_fwd", "wf_inversion_count"]
+           "wf_vqmc_train_step_apply", "wf_psi_antisym_fwd", "wf_logpdf_unsorted_fwd", "wf_inversion_count",
+           "wf_spline_create", "wf_spline_destroy", "wf_spline_n_bases", "wf_spline_apply", "wf_spline_reverse", "wf_spline_enforce_bc",
+           "wf_spline_remove_bias", "wf_spline_sample"]
 
 _lib = None
 
@@ -174,6 +182,22 @@ def lib():
     L.wf_block_sums.argtypes = [vp, i64, vp, vp, i64, vp]
     L.wf_block_sums_workspace_bytes.restype = i64
     L.wf_block_sums_workspace_bytes.argtypes = [i64]
+    L.wf_spline_create.restype = i32
+    L.wf_spline_create.argtypes = [ctypes.POINTER(SplineDesc), vp, vp, i32, ctypes.POINTER(vp)]
+    L.wf_spline_destroy.restype = None
+    L.wf_spline_destroy.argtypes = [vp]
+    L.wf_spline_n_bases.restype = i32
+    L.wf_spline_n_bases.argtypes = [vp]
+    L.wf_spline_apply.restype = i32
+    L.wf_spline_apply.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp]
+    L.wf_spline_reverse.restype = i32
+    L.wf_spline_reverse.argtypes = [vp, vp, i64, vp, ctypes.c_float, vp, vp]
+    for name in ("wf_spline_enforce_bc", "wf_spline_remove_bias"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, i64, i32, vp, vp]
+    L.wf_spline_sample.restype = i32
+    L.wf_spline_sample.argtypes = [vp, ctypes.c_uint64, vp, i64, i32, i32, vp, vp]
     if L.wf_abi_version() != 2:
         raise ImportError("libwaveflow_hip ABI version mismatch")
     _lib = L
