@@ -234,7 +234,7 @@ int wf_sample(const wf_model* m, uint64_t seed, int64_t B, float* x_dev, float* 
  * everything else on the wave-cooperative kernel: same function.
  * Coverage: WF_PRIOR_WAVEFLOW models with IMADE layers, boundary constraints the spline tables carry (any value on the I layers and, since
  * round 3, on the B-spline prior), gated heads included;
- * D = 2..8 with <= 32 bases per dimension, D = 2..4 with 33..64. */
+ * D = 2..8 with <= 64 bases per dimension (33..64 at D >= 5: the R3 sweep; WF_WIDE_RF selects the RF form). */
 int wf_hamiltonian_fwd(const wf_model* m, const float* x_dev, int64_t B, const float* protons_host, int32_t n_protons,
                        float* hpsi_dev, float* psi_dev, float* laplacian_dev, void* stream);
 
@@ -314,7 +314,7 @@ int wf_mle_train_step(wf_model* m, const wf_train_state* st, const float* x_dev,
                       void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 /* Parameter gradient of the log-density: grad_dev[p] = sum_b w_dev[b] * d log_pdf_b / d theta_p for every model wf_logpdf_fwd
- * evaluates with boundary constraints the spline tables carry (any value), gated heads included, and <= 32 bases per dimension (or <= 64 for D <= 4) (IMADE or MADE layers; Waveflow, M-spline, Normal or Uniform
+ * evaluates with boundary constraints the spline tables carry (any value), gated heads included, and <= 64 bases per dimension (IMADE or MADE layers; Waveflow, M-spline, Normal or Uniform
  * prior).  With w = -1/B this is the gradient of benchmark_tests.loss (benchmark_tests.py:84-87, 98-101); with per-walker
  * weights it is the jacrev(log_pdf) contraction of vqmc.train_step (vqmc.py:175-180). */
 int64_t wf_logpdf_vjp_workspace_bytes(const wf_model* m, int64_t B);

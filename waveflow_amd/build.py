@@ -10,7 +10,8 @@ LIB = os.path.join(HERE, "libwaveflow_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
 
 SOURCES = ["wf_tables.cpp", "wf_model.cpp", "wf_kernels_scalar.hip", "wf_scalar_inst_d2.hip", "wf_scalar_inst_d3.hip", "wf_scalar_inst_d4.hip", "wf_scalar_inst_d56.hip",
-           "wf_scalar_inst_d78.hip", "wf_scalar_inst_n64.hip", "wf_kernels_mfma.hip", "wf_mfma_inst_d2.hip", "wf_mfma_inst_d2t2.hip", "wf_mfma_inst_d34.hip",
+           "wf_scalar_inst_d78.hip", "wf_scalar_inst_n64.hip", "wf_scalar_inst_n64_d56.hip",
+           "wf_scalar_inst_n64_d78.hip", "wf_kernels_mfma.hip", "wf_mfma_inst_d2.hip", "wf_mfma_inst_d2t2.hip", "wf_mfma_inst_d34.hip",
            "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_dir.hip",
            "wf_kernels_spline.hip"]
 # -ffp-contract=off: the index arithmetic and the table lerp keep the reference's separate

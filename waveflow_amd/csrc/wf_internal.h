@@ -1,6 +1,7 @@
 // wf_internal.h -- declarations shared by the translation units of libwaveflow_hip.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/waveflow_hip.h"
@@ -186,6 +187,11 @@ int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tab
 constexpr int rf_block(int D) { return D <= 5 ? D : (D == 6 ? WF_RF_BLOCK_6 : WF_RF_BLOCK_78); }
 inline int ring_coefs(int D, int kind) { return kind == 0 ? 1 : (kind == 1 ? 3 : (kind == 2 ? rf_block(D) + 2 : D + 2)); }
 inline int ring_samples(int D, int kind) { return (kind == 0 || kind == 3) ? 1 : (kind == 1 ? D : (D + rf_block(D) - 1) / rf_block(D)); }
+// The second-order sweeps of 33 .. 64 bases (one dimension x 64 rows per pass) fit RF up to D = 4 only: for D = 5 .. 8 the RF forms keep
+// 0.3 .. 1.4 KB per lane in scratch, so those models run in R3 (kind 1) -- the energy sweep and the taped gradient sweeps alike.
+// WF_WIDE_RF (read per call by the energy sweep, at model creation for the gradients) selects the RF forms there anyway, for A/B runs.
+// (D > 8: no ring kernel exists; R3 keeps the workspace sizes those models always reported)
+inline bool second_order_rf(int D, int nbp) { return D <= 8 && (nbp == 32 || D <= 4 || getenv("WF_WIDE_RF") != nullptr); }
 // reverse pass (wf_kernels_grad.hip)
 int grad_ws_rows(int D, int nbp);
 int wgrad_partial_floats(int n_nets, int64_t net_img_floats);

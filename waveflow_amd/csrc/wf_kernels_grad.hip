@@ -380,6 +380,10 @@ int launch_wgrad(int D, int nbp, int ring_kind, int n_nets, int64_t n_samples, c
             case 2: CALLK(2, 2);
             case 3: CALLK(3, 2);
             case 4: CALLK(4, 2);
+            case 5: CALLK(5, 2);
+            case 6: CALLK(6, 2);
+            case 7: CALLK(7, 2);
+            case 8: CALLK(8, 2);
             default: return WF_ERR_UNSUPPORTED;
         }
     }

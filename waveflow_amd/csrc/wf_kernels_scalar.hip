@@ -25,7 +25,8 @@ namespace wf {
 namespace scalar {
 WF_SCALAR_SHAPE(extern, 2, 32) WF_SCALAR_SHAPE(extern, 3, 32) WF_SCALAR_SHAPE(extern, 4, 32) WF_SCALAR_SHAPE(extern, 5, 32)
 WF_SCALAR_SHAPE(extern, 6, 32) WF_SCALAR_SHAPE(extern, 7, 32) WF_SCALAR_SHAPE(extern, 8, 32)
-WF_SCALAR_SHAPE(extern, 2, 64) WF_SCALAR_SHAPE(extern, 3, 64) WF_SCALAR_SHAPE(extern, 4, 64)
+WF_SCALAR_SHAPE(extern, 2, 64) WF_SCALAR_SHAPE(extern, 3, 64) WF_SCALAR_SHAPE(extern, 4, 64) WF_SCALAR_SHAPE(extern, 5, 64)
+WF_SCALAR_SHAPE(extern, 6, 64) WF_SCALAR_SHAPE(extern, 7, 64) WF_SCALAR_SHAPE(extern, 8, 64)
 }  // namespace scalar
 
 namespace {
@@ -137,6 +138,10 @@ int finish_launch() {
             case 2: CALL(2, 64); break;                                          \
             case 3: CALL(3, 64); break;                                          \
             case 4: CALL(4, 64); break;                                          \
+            case 5: CALL(5, 64); break;                                          \
+            case 6: CALL(6, 64); break;                                          \
+            case 7: CALL(7, 64); break;                                          \
+            case 8: CALL(8, 64); break;                                          \
             default: return WF_ERR_UNSUPPORTED;                                  \
         }                                                                        \
     } else {                                                                     \

@@ -1325,12 +1325,16 @@ int64_t wave_tail_floats(int D, int ring_kind) { return (int64_t)(2 * D + 1) * r
         default: return WF_ERR_UNSUPPORTED;       \
     }
 
-// 33..64 bases per dimension (nbp == 64): the one-dimension-per-pass kernels, built for D <= 4 (as the 64-row MFMA kernel)
+// 33..64 bases per dimension (nbp == 64): the one-dimension-per-pass kernels (D >= 5: R1 and R3 on the default paths, second_order_rf)
 #define WF_WAVE_DISPATCH64(CALL)                  \
     switch (md.D) {                               \
         case 2: return CALL(2);                   \
         case 3: return CALL(3);                   \
         case 4: return CALL(4);                   \
+        case 5: return CALL(5);                   \
+        case 6: return CALL(6);                   \
+        case 7: return CALL(7);                   \
+        case 8: return CALL(8);                   \
         default: return WF_ERR_UNSUPPORTED;       \
     }
 
@@ -1380,6 +1384,10 @@ int launch_wave_sample(const ModelDev& md, const ModelDev* md_dev, const float* 
             case 2: CALLK(2, 2);
             case 3: CALLK(3, 2);
             case 4: CALLK(4, 2);
+            case 5: CALLK(5, 2);
+            case 6: CALLK(6, 2);
+            case 7: CALLK(7, 2);
+            case 8: CALLK(8, 2);
             default: return WF_ERR_UNSUPPORTED;
         }
         return finish();
@@ -1463,11 +1471,11 @@ int launch_wave_eval(const ModelDev& md, const ModelDev* md_dev, const float* ta
 
 // H psi, psi, laplacian of B walkers: forward without a tape, then the per-walker combination.  The forward sweep carries
 // (value, gradient, Laplacian / 2) per walker (RF: D + 2 channels, one pass) -- measured 1.6-1.8x faster than D passes in R3
-// (3 channels each) for every D = 2..8 (scratch/energy_ab.py).
+// (3 channels each) for every D = 2..8 (scratch/energy_ab.py).  33 .. 64 bases at D >= 5: R3, which fits the registers (second_order_rf).
 int launch_wave_energy(const ModelDev& md, const ModelDev* md_dev, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x,
                        int64_t B, const Protons& pr, float* hpsi, float* psi, float* lap, float* tail_ws, void* stream) {
     const bool force_r3 = getenv("WF_ENERGY_R3") != nullptr;   // A/B switch, read per call (tests compare the two sweeps)
-    const int kind = force_r3 ? 1 : 3;
+    const int kind = (force_r3 || !second_order_rf(md.D, md.nbp)) ? 1 : 3;
     int rc = launch_wave_fwd(md, md_dev, kind, tabI4, tabP4, fk_nat, x, B, nullptr, tail_ws, 0, stream);
     if (rc) return rc;
     return launch_energy_out(md.D, kind, tail_ws, x, B, md.constrained_mask, pr, hpsi, psi, lap, stream);

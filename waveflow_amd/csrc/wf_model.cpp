@@ -129,7 +129,7 @@ struct wf_model {
     float* d_wave = nullptr;         // NetWave images
     float* d_grad_fk = nullptr;      // [2][64] natural-order row factors for the reverse pass (flow rows, prior rows)
     float* d_egacc = nullptr;        // [n_nets][6400] gradient blocks of the matrix-core gradient path, accumulated over the chunks of a batch
-    bool wave_ok = false;            // the wave-cooperative sweeps and sampler cover this model (homogeneous constraints, gated heads included; > 32 bases: D <= 4)
+    bool wave_ok = false;            // the wave-cooperative sweeps and sampler cover this model (homogeneous constraints, gated heads included)
     // boundary conditions as a linear map on the coefficient vector (bc_map below): column sums a~ of A, per spline (I layers / prior);
     // bc_*_ok: homogeneous (no constant term) and every column with a~_j == 0 is entirely zero -> the table-driven kernels apply
     bool is_nsc = false;             // layer_kind WF_LAYER_NSC: the coupling stack (k_nsc_model), none of the conditioner-net machinery
@@ -329,7 +329,6 @@ static int64_t wave_net_floats(int D, int nbp);
 static int wave_passes(int D, int nbp) { return nbp == 32 ? (D + 1) / 2 : D; }   // output passes: 2 dimensions x 32 rows, or 1 x 64
 }  // namespace wf
 static int ensure_scratch(const wf_model* cm, int64_t floats);
-static constexpr int kTapedLaplacianMaxD = 8;    // largest D whose reverse sweep runs in RF (measured, scratch/grad_ab.py)
 static constexpr int64_t kWaveEvalMax = 6144;   // measured crossover ~7000 walkers (scratch/crossover.py)
 static constexpr int64_t kGradTileMin = 16384;    // psi / Laplacian gradients: the matrix-core path (k_efused, k_ebwd) from here on
 static constexpr int64_t kEnergyTileMin = 16384; // H psi: the tile path (8 launches, staged weight images) from here on
@@ -400,7 +399,6 @@ static int model_build(wf_model* m) {
         if (d.prior_kind == WF_PRIOR_MFLOW) nb_max = std::max(nb_max, n_bases_of(WF_SPLINE_M, d.p_degree, d.p_knots));
         m->nbp = nb_max <= 32 ? 32 : 64;
         if (nb_max > 64) return WF_ERR_UNSUPPORTED;
-        if (m->nbp == 64 && D > 4) return WF_ERR_UNSUPPORTED;
     }
     md.nbp = m->nbp;
     std::vector<double> keep_i64, keep_p64, keep_o2b;
@@ -1109,7 +1107,7 @@ static int mfma_prepare(wf_model* m, const std::vector<double>& i64, const std::
 // The wave-cooperative kernels (wf_kernels_wave.hip): <= 32 bases, constraints that only zero the end weights.
 static bool wave_capable(const wf_model* m) {
     const wf_model_desc& d = m->desc;
-    if (!m->d_wave || (m->nbp == 64 && d.n_dim > 4)) return false;   // (the 64-row sweeps are built for D <= 4)
+    if (!m->d_wave) return false;
     const bool imade = d.layer_kind == WF_LAYER_IMADE && d.n_flow_layers > 0;
     if (imade && (!m->d_tabI4 || !m->bc_i_ok)) return false;
     const bool spline_prior = d.prior_kind == WF_PRIOR_WAVEFLOW || d.prior_kind == WF_PRIOR_MFLOW;
@@ -1175,9 +1173,9 @@ static int grad_prepare(wf_model* m) {
     }
     if (!grad_capable(m) || m->n_params >= (1 << 24)) return WF_OK;
     m->grad_psi_ok = d.prior_kind == WF_PRIOR_WAVEFLOW && (d.layer_kind == WF_LAYER_IMADE || d.n_flow_layers == 0);
-    // One taped sample per walker in RF (value, gradient, Laplacian / 2: D + 2 channels), or D samples in R3 (3 channels each).
-    // Fixed per model, because workspace sizes depend on it; WF_GRAD_R3 (read here) selects R3 for A/B tests.
-    m->ring2 = (getenv("WF_GRAD_R3") || D > kTapedLaplacianMaxD) ? 1 : 2;
+    // One taped sample per walker in RF (value, gradient, Laplacian / 2: D + 2 channels), or D samples in R3 (3 channels each); 33 .. 64 bases
+    // at D >= 5: R3 (second_order_rf, wf_internal.h).  Fixed per model, because workspace sizes depend on it; WF_GRAD_R3 (read here) selects R3 for A/B tests.
+    m->ring2 = (getenv("WF_GRAD_R3") || !second_order_rf(D, m->nbp)) ? 1 : 2;
     if (m->grad_psi_ok && m->mfma_ok && energy_vjp_capable(&m->mdev)) {
         int rc = dev_alloc(m, &m->d_egacc, (size_t)energy_vjp_gacc_floats((int)m->nets.size(), m->mdev.nbk));
         if (rc) return rc;

@@ -461,8 +461,10 @@ __device__ __forceinline__ void box_reverse(const ModelDev& md, const float (&u)
         }
         const float w = o[D - 1];                          // x[D-1] - x[0]
         const float x0 = u[D - 1] * (2 * L - w + tol) - L; // u[D-1] = (mean + L - l) / (2L - w + tol) with mean - l = x[0]
+        // (x0 + o[i] rounds to 1 - 2 ulp outside [-L, L] for u[D-1] at the ends of [0, 1]: such a walker would leave the box, where
+        // psi is NaN.  The clamp is monotone: sorted rows stay sorted.)
 #pragma unroll
-        for (int i = 0; i < D; ++i) x[i] = x0 + o[i];
+        for (int i = 0; i < D; ++i) x[i] = fmaxf(fminf(x0 + o[i], L), -L);
     } else if (md.box_kind == WF_BOX_MEAN) {
         float o[D];
         float c = 0.0f, s = 0.0f;

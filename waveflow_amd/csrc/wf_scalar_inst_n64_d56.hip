@@ -1,0 +1,9 @@
+// explicit instantiations of the scalar kernels (wf_scalar_impl.h): compiled as a separate translation unit
+#include "wf_scalar_impl.h"
+
+namespace wf {
+namespace scalar {
+WF_SCALAR_SHAPE(, 5, 64)
+WF_SCALAR_SHAPE(, 6, 64)
+}  // namespace scalar
+}  // namespace wf
