@@ -219,7 +219,7 @@ int wf_inverse_fwd(const wf_model* m, const float* u_dev, int64_t B, float* x_de
  * results are reproducible for a given seed but do not follow JAX's threefry stream (parity unpinned).  The rejection loop of a
  * column is bounded (~1e5 proposals, where the reference's while_loop is not): a walker that exhausts it is written as NaN.
  * Three kernels share the work: one walker per wave (small and medium batches), one lane per walker (other large batches), and for
- * batches >= 16384 of two-particle models with <= 64 bases the staged form (wf_kernels_etile.hip: conditioners on the matrix cores, the
+ * batches >= 16384 of two-particle models with <= 64 bases the staged form (wf_kernels_etile_sample.hip: conditioners on the matrix cores, the
  * mesh searches one lane per walker; WF_SAMPLE_TILE_MIN moves the switch); the same holds for wf_inverse_fwd.  The kernels draw from the
  * same law with their own proposal sequences, so the walkers of a seed change across the switch points. */
 int wf_sample(const wf_model* m, uint64_t seed, int64_t B, float* x_dev, float* latent_dev, int32_t exact, void* stream);
@@ -246,7 +246,7 @@ int wf_hamiltonian_fwd(const wf_model* m, const float* x_dev, int64_t B, const f
  * the order beyond the last cached one clamps to it (JAX's out-of-range index semantics at isplines_jax.py:65).
  * workspace: wf_psi_vjp_workspace_bytes(m, B) bytes suffice for any B (larger batches are processed in chunks of what the
  * workspace holds).  Same model coverage as wf_hamiltonian_fwd.  Batches >= 16384 (WF_GRAD_TILE_MIN, read per call) of ungated two-particle
- * models with <= 64 bases take the matrix-core path (wf_kernels_etile.hip: k_efused, k_ebwd per net; <= 32 bases since round 3, 33..64 since
+ * models with <= 64 bases take the matrix-core path (wf_kernels_etile_bwd.hip: k_efused, k_ebwd per net; <= 32 bases since round 3, 33..64 since
  * round 4); everything else the reverse wave sweeps.  Bitwise reproducible on either path. */
 int64_t wf_psi_vjp_workspace_bytes(const wf_model* m, int64_t B);
 int wf_psi_vjp(const wf_model* m, const float* x_dev, int64_t B, const float* w_psi_dev, const float* w_lap_dev, float* grad_dev,

@@ -195,7 +195,7 @@ def test_mean_type_box_inverse_beyond_two_particles(D, monkeypatch):
 
 
 def test_staged_sampler_of_large_batches(he_flat, monkeypatch):
-    """From WF_SAMPLE_TILE_MIN walkers on (default 16 384) wf_sample / wf_inverse_fwd of the two-particle family run staged (wf_kernels_etile.hip:
+    """From WF_SAMPLE_TILE_MIN walkers on (default 16 384) wf_sample / wf_inverse_fwd of the two-particle family run staged (wf_kernels_etile_sample.hip:
     conditioners on the matrix cores, one lane per walker for the mesh searches): the inverse against the oracle and against the one-walker-per-wave
     kernel on the same latent points, the round trip through the forward pass, the draws against the wave kernel's (two-sample Kolmogorov-Smirnov),
     several passes over the model's scratch (a walker's stream is keyed by its index in the batch), and the fall-back of other models."""

@@ -77,3 +77,10 @@ def test_the_join_rule_sees_the_sequence_that_failed_and_accepts_the_padded_one(
 def test_every_kernel_that_issues_mfma_is_guarded():
     """A new matrix-core kernel under a name the guard's pattern does not match would escape both rules."""
     assert isa_guard.unguarded_mfma_kernels(wf_build.build()) == []
+
+
+def test_no_kernel_is_defined_in_two_code_objects():
+    """Every kernel is compiled in one translation unit.  A unit that includes another unit's kernels (the max-ilp reverse unit once included all of
+    wf_kernels_etile.hip) links a second copy of each non-template kernel into the library: never launched, and scanned by the guard for nothing."""
+    dups = isa_guard.duplicate_kernels(wf_build.build())
+    assert dups == {}, dups

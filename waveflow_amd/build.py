@@ -12,8 +12,8 @@ OBJ = os.path.join(CSRC, "_obj")
 SOURCES = ["wf_tables.cpp", "wf_model.cpp", "wf_kernels_scalar.hip", "wf_scalar_inst_d2.hip", "wf_scalar_inst_d3.hip", "wf_scalar_inst_d4.hip", "wf_scalar_inst_d56.hip",
            "wf_scalar_inst_d78.hip", "wf_scalar_inst_n64.hip", "wf_scalar_inst_n64_d56.hip",
            "wf_scalar_inst_n64_d78.hip", "wf_kernels_mfma.hip", "wf_mfma_inst_d2.hip", "wf_mfma_inst_d2t2.hip", "wf_mfma_inst_d34.hip",
-           "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_dir.hip",
-           "wf_kernels_spline.hip"]
+           "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip",
+           "wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_sample.hip", "wf_kernels_etile_dir.hip", "wf_kernels_spline.hip"]
 # -ffp-contract=off: the index arithmetic and the table lerp keep the reference's separate
 # multiply / add roundings; dot products that may fuse say so with explicit fmaf / MFMA.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
@@ -31,6 +31,10 @@ MFMA_FLAGS = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-p
 # per translation unit: the two-row-block reverse kernels under the max-ilp scheduling strategy (-6 % for them, +1 % for the one-row-block form)
 EXTRA_FLAGS = {"wf_etile_bwd_k2.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
+# units that include wf_etile_cond.h (the two-particle conditioner), and the two units of the reverse kernel (wf_etile_bwd.h)
+ETILE_BWD_UNITS = ("wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip")
+ETILE_COND_UNITS = ("wf_kernels_etile.hip", "wf_kernels_etile_sample.hip") + ETILE_BWD_UNITS
+
 
 def _hipcc():
     for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", "hipcc"):
@@ -44,13 +48,17 @@ def _deps(src):
     if "mfma" in src or "etile" in src:
         d.append(os.path.join(CSRC, "wf_mfma_impl.h"))
     if "etile" in src:
-        d += [os.path.join(CSRC, "wf_etile_common.h"), os.path.join(CSRC, "wf_etile_adjoint.h")]
-    if src == "wf_etile_bwd_k2.hip":
-        d.append(os.path.join(CSRC, "wf_kernels_etile.hip"))
+        d.append(os.path.join(CSRC, "wf_etile_common.h"))
+    if src in ETILE_COND_UNITS:
+        d.append(os.path.join(CSRC, "wf_etile_cond.h"))
+    if src in ETILE_BWD_UNITS:
+        d += [os.path.join(CSRC, "wf_etile_bwd.h"), os.path.join(CSRC, "wf_etile_adjoint.h")]
     if "grad" in src or "wave" in src:
         d.append(os.path.join(CSRC, "wf_ring.h"))
     if "scalar" in src or "wave" in src or "rqs" in src or "spline" in src:   # (the wave sampler and the spline closures share Philox / the lerp with the one-lane kernels)
-        d.append(os.path.join(CSRC, "wf_scalar_impl.h"))
+        d += [os.path.join(CSRC, "wf_scalar_impl.h"), os.path.join(CSRC, "wf_philox.h")]
+    if src == "wf_kernels_etile_sample.hip":
+        d.append(os.path.join(CSRC, "wf_philox.h"))
     return [p for p in d if os.path.exists(p)]
 
 

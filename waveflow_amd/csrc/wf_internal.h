@@ -162,7 +162,7 @@ bool energy_dir_capable(const MfmaDev* mdev);
 int64_t energy_dir_floats(int64_t B, int D);
 int launch_energy_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, const Protons& pr,
                       float* hpsi, float* psi, float* lap, float* ws, void* stream);
-// parameter gradients of psi and its Laplacian on the matrix cores (two-particle family, <= 64 bases; wf_kernels_etile.hip: k_efused, k_ebwd per net, k_egrad_reduce)
+// parameter gradients of psi and its Laplacian on the matrix cores (two-particle family, <= 64 bases; k_efused in wf_kernels_etile.hip, k_ebwd per net and k_egrad_reduce in wf_kernels_etile_bwd.hip)
 bool energy_vjp_capable(const MfmaDev* mdev);
 int64_t energy_vjp_floats_per_walker(int n_nets);
 int64_t energy_vjp_fixed_floats(int n_nets, int nbk);
@@ -206,7 +206,7 @@ int launch_zgrad_reduce(const float* zws, int64_t n_samples, int n_rows, int acc
 int launch_zgrad_scatter(const float* zgrad, int n_rows, const int32_t* zmap, const int32_t* zraw_off, const float* plain, float* grad_flat, void* stream);
 int launch_wave_energy(const ModelDev& md, const ModelDev* md_dev, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x,
                        int64_t B, const Protons& pr, float* hpsi, float* psi, float* lap, float* tail_ws, void* stream);
-// staged inverse / sampler of large two-particle batches (wf_kernels_etile.hip: conditioners on the matrix cores, one lane per walker elsewhere)
+// staged inverse / sampler of large two-particle batches (wf_kernels_etile_sample.hip: conditioners on the matrix cores, one lane per walker elsewhere)
 bool tile_sample_capable(const MfmaDev* mdev);
 int64_t tile_sample_floats(int64_t B, int nbk);
 int launch_tile_sample(const MfmaDev* mdev, const ModelDev& md, const float* tabI0, const float* tabP0, const float* fk_nat, int draw, unsigned long long seed,

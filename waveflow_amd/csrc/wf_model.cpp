@@ -902,7 +902,7 @@ static void describe_mfma_image(const wf_model* m, int n, uint32_t base, std::ve
 
 // Decides whether the MFMA kernel covers this model and builds its parameter-independent parts.
 // i64 / p64: the fp64 tables already built by model_build (I: [4][nb][n_mesh]; prior: OB or M), o2b: [nb][nb].
-// Transposed operand images of net n for the reverse sweep of the matrix-core gradient path (k_ebwd, wf_kernels_etile.hip; D = 2, <= 64 bases):
+// Transposed operand images of net n for the reverse sweep of the matrix-core gradient path (k_ebwd, wf_etile_bwd.h; D = 2, <= 64 bases):
 // hbar_1[k] = sum_u W1'[k][u] zbar_2[u] and hbar_2[k] = sum_j W2'[k][j] obar[j] are MFMA products whose A operand is the weight matrix with the
 // INPUT unit on the row, same entries and scales as the forward image.  Layout (floats, base = float offset inside d_mfma; nbk = 32-row blocks of the head):
 //   TW1 hi [ob 2][t 2][s 2][lane 64][8 halves] (2048 floats), TW1 lo (2048), TW2 hi [ob 2][kb nbk][s 2][64][8] (1024 nbk), TW2 lo (1024 nbk), W0'[0][unit] in
@@ -1552,7 +1552,7 @@ static int64_t wave_sample_max() {   // tuning knob (read at every call): WF_WAV
 }
 
 // Large batches of the two-particle family (the family of the matrix-core local energy, <= 64 bases): the staged inverse / sampler of
-// wf_kernels_etile.hip (conditioners on the matrix cores, one lane per walker for the searches).  WF_SAMPLE_TILE_MIN (read per call) moves the switch
+// wf_kernels_etile_sample.hip (conditioners on the matrix cores, one lane per walker for the searches).  WF_SAMPLE_TILE_MIN (read per call) moves the switch
 // point; 0 disables the path.  It reads the MFMA image and the composite dimension-0 tables: not while they are stale (deferred training steps).
 static constexpr int64_t kTileSampleMin = 16384;
 static constexpr int64_t kTileSampleChunk = 1 << 18;   // walkers per pass of a call without a caller's workspace (the model's scratch: 111 MB)
@@ -1730,7 +1730,7 @@ static int64_t vjp_bytes_per_walker(const wf_model* m, bool second_order) {
     return (samples * ((int64_t)m->nets.size() * grad_ws_rows(D, m->nbp) * nc + zrows) + wave_tail_floats(D, kind) + 4) * (int64_t)sizeof(float);
 }
 
-// the matrix-core gradient path (wf_kernels_etile.hip) applies to this model at this batch size: capability + the knob WF_GRAD_TILE_MIN (read per call),
+// the matrix-core gradient path (wf_kernels_etile_bwd.hip) applies to this model at this batch size: capability + the knob WF_GRAD_TILE_MIN (read per call),
 // independent of transient state (stale evaluation tables, fp16 range of the current parameters)
 static bool grad_tile_capable_at(const wf_model* m, int64_t B) {
     if (!m->d_egacc) return false;
@@ -1778,7 +1778,7 @@ static int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const 
         return WF_OK;
     }
     // Large batches of the two-particle family (the family of the one-kernel H psi, <= 64 bases): forward, reverse and weight-gradient products on the
-    // matrix cores (wf_kernels_etile.hip: k_efused with the per-net input jets, k_ebwd per net with the weight-gradient products inside).  WF_GRAD_TILE_MIN (read per call) moves the
+    // matrix cores (wf_kernels_etile_bwd.hip: k_efused with the per-net input jets, k_ebwd per net with the weight-gradient products inside).  WF_GRAD_TILE_MIN (read per call) moves the
     // switch point; 0 disables the path.
     if ((mode == 1 || mode == 2) && second_order && m->d_egacc) {
         const int64_t tile_min = 1;

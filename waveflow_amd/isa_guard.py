@@ -8,6 +8,7 @@ module checks the result: it extracts the gfx950 code objects from the linked li
 and counts the three opcodes inside every function whose name matches GUARDED.  `build.build()` calls `check()` after every link and
 refuses the library on a hit; `tests/test_isa_guard.py` runs the same check in the CPU suite.
 """
+import contextlib
 import os
 import re
 import shutil
@@ -25,24 +26,44 @@ def _objdump():
     return p if os.path.exists(p) else shutil.which("llvm-objdump")
 
 
-def scan(lib):
-    """-> {kernel symbol: [offending disassembly lines]} over the guarded kernels of `lib`, and the number of guarded kernels seen."""
+@contextlib.contextmanager
+def _code_objects(lib):
+    """The gfx950 code objects of the linked library `lib`, extracted into a temporary directory (paths, valid inside the `with`)."""
     od = _objdump()
     if od is None:
         raise RuntimeError("llvm-objdump not found (set WF_LLVM_BIN)")
-    hits, n_guarded = {}, 0
     with tempfile.TemporaryDirectory(prefix="wf_isa_") as tmp:
         local = os.path.join(tmp, "lib.so")
         shutil.copy(lib, local)
         subprocess.run([od, "--offloading", local], cwd=tmp, check=True, capture_output=True)
-        for f in sorted(os.listdir(tmp)):
-            if "amdgcn" not in f:
-                continue
+        yield [os.path.join(tmp, f) for f in sorted(os.listdir(tmp)) if "amdgcn" in f]
+
+
+def duplicate_kernels(lib):
+    """-> {kernel symbol: number of code objects} for the kernels of `lib` defined in more than one gfx950 code object (by their descriptors,
+    <symbol>.kd).  A kernel with internal linkage (anonymous namespace) gets a copy of its own in every translation unit that defines it."""
+    od = _objdump()
+    count = {}
+    with _code_objects(lib) as cos:
+        for co in cos:
+            for line in subprocess.run([od, "-t", co], capture_output=True, text=True, check=True).stdout.splitlines():
+                name = line.split()[-1] if line.strip() else ""
+                if name.endswith(".kd"):
+                    count[name[:-3]] = count.get(name[:-3], 0) + 1
+    return {k: n for k, n in count.items() if n > 1}
+
+
+def scan(lib):
+    """-> {kernel symbol: [offending disassembly lines]} over the guarded kernels of `lib`, and the number of guarded kernels seen."""
+    od = _objdump()
+    hits, n_guarded = {}, 0
+    with _code_objects(lib) as cos:
+        for co in cos:
             # only code objects that define a guarded kernel are disassembled (the symbol table is cheap, the disassembly is not)
-            syms = subprocess.run([od, "-t", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
+            syms = subprocess.run([od, "-t", co], capture_output=True, text=True, check=True).stdout
             if not GUARDED.search(syms):
                 continue
-            text = subprocess.run([od, "-d", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
+            text = subprocess.run([od, "-d", co], capture_output=True, text=True, check=True).stdout
             cur, guarded = None, False
             for line in text.splitlines():
                 m = _SYM.match(line)
@@ -146,17 +167,12 @@ def scan_mfma_joins(lib):
     """-> {kernel: [description of a read of an MFMA destination inside its window behind a branch]} over the guarded kernels of `lib`."""
     od = _objdump()
     hits = {}
-    with tempfile.TemporaryDirectory(prefix="wf_isa_") as tmp:
-        local = os.path.join(tmp, "lib.so")
-        shutil.copy(lib, local)
-        subprocess.run([od, "--offloading", local], cwd=tmp, check=True, capture_output=True)
-        for f in sorted(os.listdir(tmp)):
-            if "amdgcn" not in f:
-                continue
-            syms = subprocess.run([od, "-t", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
+    with _code_objects(lib) as cos:
+        for co in cos:
+            syms = subprocess.run([od, "-t", co], capture_output=True, text=True, check=True).stdout
             if not GUARDED.search(syms):
                 continue
-            hits.update(join_hits_in_text(subprocess.run([od, "-d", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout))
+            hits.update(join_hits_in_text(subprocess.run([od, "-d", co], capture_output=True, text=True, check=True).stdout))
     return hits
 
 
@@ -164,15 +180,10 @@ def unguarded_mfma_kernels(lib):
     """Kernels of `lib` that issue MFMA instructions but are not matched by GUARDED (the rules above would not see them)."""
     od = _objdump()
     out = set()
-    with tempfile.TemporaryDirectory(prefix="wf_isa_") as tmp:
-        local = os.path.join(tmp, "lib.so")
-        shutil.copy(lib, local)
-        subprocess.run([od, "--offloading", local], cwd=tmp, check=True, capture_output=True)
-        for f in sorted(os.listdir(tmp)):
-            if "amdgcn" not in f:
-                continue
+    with _code_objects(lib) as cos:
+        for co in cos:
             cur = None
-            for line in subprocess.run([od, "-d", "--no-show-raw-insn", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout.splitlines():
+            for line in subprocess.run([od, "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout.splitlines():
                 m = _SYM.match(line)
                 if m:
                     cur = m.group(1)
