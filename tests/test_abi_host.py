@@ -138,3 +138,26 @@ def test_table_cache_files_are_the_reference_fixture_files(tmp_path, golden):
     assert os.path.basename(m[0]) == "degree_3_niknots_16_nmp_2000_nd_0.npy" and np.load(m[0]).shape == (16, 2000)   # n_knots - k = 15 + 2 (k - 1) - k
     with pytest.raises(FileNotFoundError):
         tc.load_cached_bases(str(tmp_path / "I"), "I", 6, 23)
+
+
+def test_environment_switches_live_in_wf_env_h_and_readme_lists_them():
+    """csrc/wf_env.h is the only file of csrc/ that reads the environment, and README's "Environment switches" table names exactly its knobs
+    (plus the ones Python, the build and bench.py read, excluded by name below)."""
+    csrc = os.path.join(ROOT, "waveflow_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, f)
+        if os.path.isfile(path) and f != "wf_env.h":
+            assert "getenv" not in open(path, errors="replace").read(), f
+    env_h = open(os.path.join(csrc, "wf_env.h")).read()
+    assert "getenv" in env_h
+    in_header = set(re.findall(r'"(WF_[A-Z0-9_]+)"', env_h))   # the names the accessors pass to env_raw / env_set / env_i64 / env_int
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    table = readme[readme.index("## Environment switches"):]
+    rows = [line for line in table.splitlines() if line.startswith("| `WF_")]
+    in_readme = set()
+    for line in rows:
+        in_readme |= set(re.findall(r"WF_[A-Z0-9_]+", line.split("|")[1]))
+    not_the_library = {"WF_LIB", "WF_LIB_EXPERIMENT", "WF_SKIP_ISA_GUARD", "WF_CXXFLAGS", "WF_GRAPH_COLLECTIVE", "WF_FORCE_DIST"}
+    not_the_library |= {n for n in in_readme if n.startswith("WF_BENCH_")}
+    assert len(in_header) >= 20
+    assert in_header == in_readme - not_the_library, (sorted(in_header - in_readme), sorted(in_readme - not_the_library - in_header))

@@ -225,7 +225,7 @@ def test_local_energy_tile_path_other_models(monkeypatch):
         for a, b in ((ps, pw), (lap, lw), (hp, hw)):
             d = np.abs(a - b)
             assert np.isfinite(a).all() and d.max() <= 5e-4 * np.abs(b).max() and np.median(d) <= 1e-6 * np.abs(b).max(), (c, d.max() / np.abs(b).max())
-        # the head kernels read every table chunk at the mesh index clamped to the chunk's support (wf_model.cpp: upload_chunked): the same
+        # the head kernels read every table chunk at the mesh index clamped to the chunk's support (wf_model_build.cpp: upload_chunked): the same
         # bits as the reads at the walker's own index (a model created with the clamp switched off)
         monkeypatch.setenv("WF_MFMA_NO_BAND", "1")
         params2, psi2, _, _ = init(4, 2)

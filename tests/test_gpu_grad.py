@@ -796,7 +796,7 @@ def test_abi_error_paths_of_the_gradient_entry_points(he_flat):
                        p_knots=15, p_left={0: 0.0, 2: 0.0}, p_right={}, i_gate=True, p_gate=True)
     _directional_check(lp5, p5, om5, X3, seed=13)
     # a constraint with a non-zero value adds a constant term b to the map.  I- and M-spline coefficients reach the constraints normalised
-    # (sum 1), so the table-driven kernels fold b into the linear part (A + b 1^T: wf_model.cpp bc_map), gradients included
+    # (sum 1), so the table-driven kernels fold b into the linear part (A + b 1^T: wf_model_build.cpp bc_map), gradients included
     p4, lp4, _ = model_factory.get_model(n_flow_layers=1, i_constraint_dict_left={0: 0.0, 1: 0.5}, i_constraint_dict_right={0: 1.0, 1: 0.25},
                                          prior_constraint_dict_left={0: 0.3})(0, 2)
     om4 = oracle.Model(D=2, n_layers=1, i_k=5, i_knots=15, i_reg=0.0, i_left={0: 0.0, 1: 0.5}, i_right={0: 1.0, 1: 0.25}, prior="mflow", p_k=5,

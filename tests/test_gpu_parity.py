@@ -322,7 +322,7 @@ def test_mflow_and_flow_density_heads_vs_oracle(golden, kernel):
 @pytest.mark.parametrize("kernel", KERNELS_ALL)
 def test_general_boundary_constraint_dicts(kernel, D, knots):
     """tests/test_boundary_constraints.py:30-31 style dicts: {0:0, 2:0, 3:0} left, {0:0} right on the prior.  Every kernel: the
-    table-driven ones (mfma, wave) carry the boundary map in their tables (wf_model.cpp: bc_map).  (3, 34): three particles, 39 / 38 bases (the orthogonalisation needs an even number of B bases, ortho_splines.py:61-63)
+    table-driven ones (mfma, wave) carry the boundary map in their tables (wf_model_build.cpp: bc_map).  (3, 34): three particles, 39 / 38 bases (the orthogonalisation needs an even number of B bases, ortho_splines.py:61-63)
     per dimension, i.e. the two-row-block layouts."""
     from waveflow_amd import flows, model_factory, wavefunctions, flatten_params
     mt = model_factory.get_masked_transform
@@ -357,7 +357,7 @@ def test_general_boundary_constraint_dicts(kernel, D, knots):
 def test_boundary_constraints_with_nonzero_values(kernel):
     """Dictionaries with a non-zero value on the normalised splines (I layers: first derivative 0.5 / 0.25 at the ends, M prior: value 0.3
     at the left end).  The per-walker kernel runs the literal overwrite sequence (isplines_jax.py:158-194, msplines_jax.py:156-184); the
-    table-driven kernels carry the constant term folded into their tables (wf_model.cpp: bc_map) -- all against the C oracle's literal form."""
+    table-driven kernels carry the constant term folded into their tables (wf_model_build.cpp: bc_map) -- all against the C oracle's literal form."""
     import os
     from conftest import GOLDEN
     from waveflow_amd import model_factory, flatten_params
@@ -508,7 +508,7 @@ def test_walkers_outside_the_box_wrap_like_the_reference(he_flat, kernel):
 
 @pytest.mark.parametrize("D,knots", [(2, 23), (3, 23), (2, 33)])
 def test_mfma_support_clamped_table_reads_change_no_bit(D, knots):
-    """The MFMA kernel reads every 4-row piece of a spline-table row at the mesh index clamped to the piece's support (wf_model.cpp:
+    """The MFMA kernel reads every 4-row piece of a spline-table row at the mesh index clamped to the piece's support (wf_model_images.cpp:
     piece_bounds; walkers outside the support then share two cache lines).  Outside its support a basis row holds the bits of the clamped
     entry, so log_pdf, psi, u and the bin indices must equal, bit for bit, those of a model created with the clamp switched off
     (WF_MFMA_NO_BAND at creation) -- also with derivative constraints folded into the tables."""

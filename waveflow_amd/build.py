@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwaveflow_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
 
-SOURCES = ["wf_tables.cpp", "wf_model.cpp", "wf_kernels_scalar.hip", "wf_scalar_inst_d2.hip", "wf_scalar_inst_d3.hip", "wf_scalar_inst_d4.hip", "wf_scalar_inst_d56.hip",
+SOURCES = ["wf_tables.cpp", "wf_runtime.cpp", "wf_model_build.cpp", "wf_model_images.cpp", "wf_dispatch.cpp", "wf_train.cpp", "wf_kernels_scalar.hip", "wf_scalar_inst_d2.hip", "wf_scalar_inst_d3.hip", "wf_scalar_inst_d4.hip", "wf_scalar_inst_d56.hip",
            "wf_scalar_inst_d78.hip", "wf_scalar_inst_n64.hip", "wf_scalar_inst_n64_d56.hip",
            "wf_scalar_inst_n64_d78.hip", "wf_kernels_mfma.hip", "wf_mfma_inst_d2.hip", "wf_mfma_inst_d2t2.hip", "wf_mfma_inst_d34.hip",
            "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip",
@@ -31,10 +31,6 @@ MFMA_FLAGS = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-p
 # per translation unit: the two-row-block reverse kernels under the max-ilp scheduling strategy (-6 % for them, +1 % for the one-row-block form)
 EXTRA_FLAGS = {"wf_etile_bwd_k2.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
-# units that include wf_etile_cond.h (the two-particle conditioner), and the two units of the reverse kernel (wf_etile_bwd.h)
-ETILE_BWD_UNITS = ("wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip")
-ETILE_COND_UNITS = ("wf_kernels_etile.hip", "wf_kernels_etile_sample.hip") + ETILE_BWD_UNITS
-
 
 def _hipcc():
     for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", "hipcc"):
@@ -43,23 +39,26 @@ def _hipcc():
     return "hipcc"
 
 
-def _deps(src):
-    d = [os.path.join(CSRC, src), os.path.join(CSRC, "wf_internal.h"), os.path.join(HERE, "..", "include", "waveflow_hip.h")]
-    if "mfma" in src or "etile" in src:
-        d.append(os.path.join(CSRC, "wf_mfma_impl.h"))
-    if "etile" in src:
-        d.append(os.path.join(CSRC, "wf_etile_common.h"))
-    if src in ETILE_COND_UNITS:
-        d.append(os.path.join(CSRC, "wf_etile_cond.h"))
-    if src in ETILE_BWD_UNITS:
-        d += [os.path.join(CSRC, "wf_etile_bwd.h"), os.path.join(CSRC, "wf_etile_adjoint.h")]
-    if "grad" in src or "wave" in src:
-        d.append(os.path.join(CSRC, "wf_ring.h"))
-    if "scalar" in src or "wave" in src or "rqs" in src or "spline" in src:   # (the wave sampler and the spline closures share Philox / the lerp with the one-lane kernels)
-        d += [os.path.join(CSRC, "wf_scalar_impl.h"), os.path.join(CSRC, "wf_philox.h")]
-    if src == "wf_kernels_etile_sample.hip":
-        d.append(os.path.join(CSRC, "wf_philox.h"))
-    return [p for p in d if os.path.exists(p)]
+def _deps(obj):
+    """Prerequisites of an object file as the compiler recorded them at its last build (-MD -MF <obj>.d: source, project and system headers),
+    or None when that record is missing or unreadable: the unit is then compiled again."""
+    try:
+        text = open(obj + ".d").read()
+    except OSError:
+        return None
+    words = text.replace("\\\n", " ").split()   # make syntax: "target: prerequisite ...", lines continued with a backslash
+    if len(words) < 2 or not words[0].endswith(":"):
+        return None
+    return words[1:]
+
+
+def _stale(obj):
+    deps = _deps(obj)
+    try:
+        t = os.path.getmtime(obj)
+        return deps is None or any(os.path.getmtime(d) > t for d in deps)
+    except OSError:   # no object yet, or a recorded header that no longer exists
+        return True
 
 
 STAMP = os.path.join(HERE, "libwaveflow_hip.flags")   # next to the library (it travels with it; csrc/_obj does not)
@@ -94,9 +93,9 @@ def build(force=False, verbose=False):
     jobs = []
     for s in srcs:
         o = os.path.join(OBJ, s + ".o")
-        if force or not os.path.exists(o) or any(os.path.getmtime(o) < os.path.getmtime(d) for d in _deps(s)):
+        if force or _stale(o):
             cmd = [_hipcc()] + FLAGS + (MFMA_FLAGS if ("mfma" in s or "etile" in s) else []) + EXTRA_FLAGS.get(s, []) + (["-x", "hip"] if s.endswith(".cpp") else [])
-            cmd += ["-c", os.path.join(CSRC, s), "-o", o]
+            cmd += ["-MD", "-MF", o + ".d", "-c", os.path.join(CSRC, s), "-o", o]
             jobs.append(cmd)
 
     def run(cmd):
@@ -108,7 +107,7 @@ def build(force=False, verbose=False):
         return r
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, len(jobs))) as ex:
+        with ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, 16, len(jobs))) as ex:
             list(ex.map(run, jobs))
     objs = [os.path.join(OBJ, s + ".o") for s in srcs]
     if jobs or force or not os.path.exists(LIB) or any(os.path.getmtime(LIB) < os.path.getmtime(o) for o in objs):

@@ -383,7 +383,7 @@ class DeviceModel:
         torch = _torch()
         ws = torch.empty(int(nbytes), device=device, dtype=torch.uint8)
         if os.environ.get("WF_POISON"):
-            ws.fill_(0xFF)   # NaN patterns: see dev_alloc in wf_model.cpp
+            ws.fill_(0xFF)   # NaN patterns: see dev_alloc_bytes in wf_runtime.cpp
         return ws
 
     def block_sums(self, v):

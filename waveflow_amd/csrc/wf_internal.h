@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/waveflow_hip.h"
+#include "wf_env.h"
 
 namespace wf {
 
@@ -14,7 +15,7 @@ int n_bases_of(int kind, int k, int n_internal);
 int build_raw_table(int kind, int k, int n_internal, int n_mesh, double* out);
 int build_ortho_b(int k, int n_internal, int n_mesh, const double* Bt, double* ob, double* b_to_ob, double* ob_to_b);
 
-// ---- device-side model image (wf_model.cpp fills it, kernels read it)
+// ---- device-side model image (wf_model_build.cpp and wf_model_images.cpp fill it, kernels read it)
 constexpr int kHidden = 64;      // MaskedDense width, model_factory.py:72
 constexpr int kMaxLayers = 16;   // flow layers
 constexpr int kMaxNets = kMaxLayers + 1;
@@ -86,7 +87,7 @@ struct ModelDev {
     SplineDev isp;                // flow-layer I-spline (IMADE)
     SplineDev psp;                // prior spline: orthogonal-B (WAVEFLOW) or M (MFLOW)
     const float* ob_to_b;         // [nbp][nbp] fp32, zero beyond nb (WAVEFLOW): row a = ob_to_b[a][:]
-    const float* ob_to_b_t;       // the same with the boundary map folded into its rows (wf_model.cpp: bc_map): table-driven kernels
+    const float* ob_to_b_t;       // the same with the boundary map folded into its rows (wf_model_build.cpp: bc_map): table-driven kernels
     const float* b_to_ob;         // [nbp][nbp] fp32, zero beyond nb (WAVEFLOW): the sampler's bound (bsplines_jax.py:164-166)
     const float* p_cb;            // [nbp] or null: constant term of the B prior's boundary map, b @ ob_to_b (a constraint with a non-zero value,
                                   // bsplines_jax.py:173-199): c = (A o) @ ob_to_b + (sum o) * p_cb -- the net's outputs reach the constraints divided by their sum
@@ -111,7 +112,7 @@ struct MfmaDev {
     int const_floats;          // fkI[nbk][2][16], fkP[nbk][2][16], ob_to_b image [nbk][nbk]{hi, lo}[2 K steps][64 lanes][8 halves], piece bounds int32 [2 tables][nbk][2][16]
     int staged;                // 0: every net resident in LDS; 1: one LDS slot, nets re-staged per super-chunk of tiles
     int staged_groups;         // staged mode: tile groups per wave and super-chunk (set per launch, 1 .. kStagedGroups)
-    const float* tabI;         // [n_mesh][8 nbk pieces][nd 0..1][side: m, m + 1][4 rows] fp32: fk_row * I_row (wf_model.cpp: pack_rows_pairs)
+    const float* tabI;         // [n_mesh][8 nbk pieces][nd 0..1][side: m, m + 1][4 rows] fp32: fk_row * I_row (wf_model_images.cpp: pack_rows_pairs)
     const float* rsI;          // [n_mesh]{R0_m, R1_m, R0_{m+1}, R1_{m+1}}: sum over rows of tabI (orders 0, 1), both lerp ends in one 16-byte record
     const float* tabP;         // [n_mesh][8 nbk pieces][side][4 rows] fp32, prior rows (B as is; M: fk_row * M_row), nd 0
     const float4_t* comp;      // [n_nets][n_mesh] composite tables of output dimension 0 (k_prepare_dim0)
@@ -191,7 +192,7 @@ inline int ring_samples(int D, int kind) { return (kind == 0 || kind == 3) ? 1 :
 // 0.3 .. 1.4 KB per lane in scratch, so those models run in R3 (kind 1) -- the energy sweep and the taped gradient sweeps alike.
 // WF_WIDE_RF (read per call by the energy sweep, at model creation for the gradients) selects the RF forms there anyway, for A/B runs.
 // (D > 8: no ring kernel exists; R3 keeps the workspace sizes those models always reported)
-inline bool second_order_rf(int D, int nbp) { return D <= 8 && (nbp == 32 || D <= 4 || getenv("WF_WIDE_RF") != nullptr); }
+inline bool second_order_rf(int D, int nbp) { return D <= 8 && (nbp == 32 || D <= 4 || env_wide_rf()); }
 // reverse pass (wf_kernels_grad.hip)
 int grad_ws_rows(int D, int nbp);
 int wgrad_partial_floats(int n_nets, int64_t net_img_floats);

@@ -74,12 +74,12 @@ __global__ __launch_bounds__(256) void k_etile_flow(const float4_t* __restrict__
         y0 = jlift(t0, t1, t2, u0);
         ld = ld + jlog(jlift(t1, t2, t3, u0) + 1e-7f);
     }
-    // ---- dimension 1: c_j = g_j (v_j / S0 + reg) / Q (calculate_bijection_params, + reg, remove_bias, boundary map: wf_model.cpp).
+    // ---- dimension 1: c_j = g_j (v_j / S0 + reg) / Q (calculate_bijection_params, + reg, remove_bias, boundary map: wf_model_build.cpp).
     // One pass over the rows: with V_k = sum_j v_j g_j B^(k)_j, R_k = sum_j g_j B^(k)_j, Qv = sum_j v_j g_j, G = sum_j g_j, S0 = sum_j v_j the
     // numerators are N_k = V_k / S0 + reg R_k and the normaliser Q = Qv / S0 + reg G.  Four rows per step: the lane's table rows come as
     // 16-byte loads (8 per step: 4 orders x the two mesh rows; rows >= nb are zero padding).
     const LerpN L = nlerp(u1.v, n_mesh);
-    const int* bnd = reinterpret_cast<const int*>(tabI + (size_t)n_mesh * 128);   // [8 chunks][lo, hi] behind the table (wf_model.cpp: upload_chunked)
+    const int* bnd = reinterpret_cast<const int*>(tabI + (size_t)n_mesh * 128);   // [8 chunks][lo, hi] behind the table (wf_model_build.cpp: upload_chunked)
     // sums over the rows (see T2): S^(a) = sum v_j^(a), Qv^(a) = sum g_j v_j^(a), V[a][k] = sum v_j^(a) g_j T_j^(k) for a + k <= 3 (k <= 3 - a ... the
     // nine pairs the two numerators need), R[k] = sum g_j T_j^(k), G = sum g_j
     float S[3] = {0.0f, 0.0f, 0.0f}, Qv[3] = {0.0f, 0.0f, 0.0f}, R[4] = {0.0f, 0.0f, 0.0f, 0.0f}, G = 0.0f;
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
     const float* fkI = lds;
     const float* fkP = lds + 32 * NBK;
     const _Float16* obh = reinterpret_cast<const _Float16*>(lds + 64 * NBK);
-    const float* cbP = lds + 64 * NBK + NBK * NBK * 1024 + 64 * NBK;   // [NBK][2][16] constant term of the B prior's boundary map times ob_to_b (mm.p_bias; wf_model.cpp)
+    const float* cbP = lds + 64 * NBK + NBK * NBK * 1024 + 64 * NBK;   // [NBK][2][16] constant term of the B prior's boundary map times ob_to_b (mm.p_bias; wf_model_images.cpp: mfma_prepare)
     const int lane = threadIdx.x & 63;
     const int j = lane & 31, h = lane >> 5;
     const int n_mesh = mm.n_mesh;
@@ -393,10 +393,9 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
 }  // namespace
 
 bool energy_tile_fused(const MfmaDev* mdev) {
-    const char* e = getenv("WF_ENERGY_FUSED");
     // (two row blocks per dimension: the static LDS of k_efused<2> -- 256 B of chunk bounds -- has to fit beside the resident nets too)
     const bool fits = (mdev->const_floats + mdev->net_floats * mdev->n_nets) * 4 + 512 <= 160 * 1024;
-    return !mdev->staged && fits && !(e && atoi(e) == 0);
+    return !mdev->staged && fits && env_energy_fused();
 }
 
 // workspace: state (12 floats), head triples (96 floats), the sign sum (1 float) per walker

@@ -733,10 +733,10 @@ int launch_tile_sample_t(const MfmaDev* mdev, const ModelDev& md, const TsArgs& 
     float* lat = cur1 + B;           // [B] (column 0 between the two prior phases)
     float* s1 = lat + 2 * B;
     float* oj = ws + (((size_t)10 * B + 63) / 64) * 64;
-    float* ow = (mdev->p_plain_bc && !getenv("WF_SAMPLE_DENSE_ENVELOPE")) ? oj + (size_t)((B + 31) / 32) * 32 * NB : nullptr;   // (behind the one channel oj holds: sized for three)
+    float* ow = (mdev->p_plain_bc && !env_sample_dense_envelope()) ? oj + (size_t)((B + 31) / 32) * 32 * NB : nullptr;   // (behind the one channel oj holds: sized for three)
     TsArgs a = a_in;
     a.ow = ow;
-    a.tabB0 = (ow && !getenv("WF_SAMPLE_FULL_ROWS")) ? mdev->tabB0 : nullptr;
+    a.tabB0 = (ow && !env_sample_full_rows()) ? mdev->tabB0 : nullptr;
     const unsigned lane_blocks = (unsigned)((B + 255) / 256);
     const int lds_bytes = (mdev->const_floats + mdev->net_floats) * (int)sizeof(float);
     static DynLdsSlots cfg_flow{}, cfg_prior{};
@@ -748,7 +748,7 @@ int launch_tile_sample_t(const MfmaDev* mdev, const ModelDev& md, const TsArgs& 
     if (draw) {
         hipLaunchKernelGGL((k_tsample<0, NB>), dim3(lane_blocks), dim3(256), 0, s, a, 0, (const float*)oj, u, B, cur0, cur1, cin, lat, latent, x);
         hipLaunchKernelGGL((k_etile_cond<true, NBK, 1>), dim3(cond_blocks), dim3(kCondWaves * 64), lds_bytes, s, *mdev, L, (const float*)cin, B, oj, s1, ow);
-        if (a.ow && a.tabB0 && !getenv("WF_SAMPLE_ONE_LANE"))   // (the band form: eight lanes per walker)
+        if (a.ow && a.tabB0 && !env_sample_one_lane())   // (the band form: eight lanes per walker)
             hipLaunchKernelGGL((k_tsample_p1g<NB>), dim3((unsigned)((B * 8 + 255) / 256)), dim3(256), 0, s, a, (const float*)oj, B, cur0, cur1, cin, (const float*)lat, latent);
         else
             hipLaunchKernelGGL((k_tsample<1, NB>), dim3(lane_blocks), dim3(256), 0, s, a, 0, (const float*)oj, u, B, cur0, cur1, cin, lat, latent, x);
@@ -759,7 +759,7 @@ int launch_tile_sample_t(const MfmaDev* mdev, const ModelDev& md, const TsArgs& 
         hipLaunchKernelGGL((k_etile_cond<false, NBK, 1>), dim3(cond_blocks), dim3(kCondWaves * 64), lds_bytes, s, *mdev, l, (const float*)cin, B, oj, s1);
         // (the band form with eight lanes per walker: two row blocks only -- 2^17 draws 0.320 -> 0.290 ms; with one row block the walker's own lane is faster,
         // 0.201 against 0.225: WF_SAMPLE_GROUP_PHASE2 forces it, WF_SAMPLE_ONE_LANE the other form)
-        if (a.i_band_int > 0 && !getenv("WF_SAMPLE_ONE_LANE") && (NB > 32 || getenv("WF_SAMPLE_GROUP_PHASE2")))
+        if (a.i_band_int > 0 && !env_sample_one_lane() && (NB > 32 || env_sample_group_phase2()))
             hipLaunchKernelGGL((k_tsample_p2g<NB>), dim3((unsigned)((B * 8 + 255) / 256)), dim3(256), 0, s, a, l, (const float*)oj, B, cur0, cur1, cin, x);
         else
             hipLaunchKernelGGL((k_tsample<2, NB>), dim3(lane_blocks), dim3(256), 0, s, a, l, (const float*)oj, u, B, cur0, cur1, cin, lat, latent, x);
@@ -782,7 +782,7 @@ int launch_tile_sample(const MfmaDev* mdev, const ModelDev& md, const float* tab
     a.nbI = md.isp.nb;
     a.nbP = md.psp.nb;
     a.degP = md.psp.degree;
-    a.i_band_int = (mdev->i_plain_bc && md.isp.degree <= 7 && !getenv("WF_SAMPLE_FULL_ROWS")) ? md.isp.nb - md.isp.degree : 0;
+    a.i_band_int = (mdev->i_plain_bc && md.isp.degree <= 7 && !env_sample_full_rows()) ? md.isp.nb - md.isp.degree : 0;
     a.n_layers = md.n_layers;
     a.i_reg = md.i_reg;
     a.tol = md.reverse_tol;

@@ -8,7 +8,7 @@
 //     registers), so an accumulator tile -- after the activation -- IS the next B operand: the whole
 //     D -> 64 -> 64 -> D*n_bases chain runs with no LDS transposes and no cross-lane traffic;
 //   * the A operand (weights) is pre-permuted on the host into that k order and streamed from LDS
-//     (wf_model.cpp: build_mfma_image).
+//     (wf_model_images.cpp: describe_mfma_image).
 // Precision.  On gfx950 the f32-input MFMA runs at the f32 VALU rate and does not overlap with VALU work
 // (measured: profiles/r01_ubench_coexec.txt), so the two K=64 layers use v_mfma_f32_32x32x16_f16 with a
 // two-way fp16 split of both operands: x = hi + lo (hi = rn16(x), lo = rn16(x - hi); fp16 subnormals are not
@@ -129,7 +129,7 @@ __device__ __forceinline__ float row_dot(const float* __restrict__ row, const fl
     return acc;
 }
 
-// tab_i / tab_p: the natural-order tables [orders][n_mesh][nbp] with the boundary map folded into their rows (wf_model.cpp: bc_map; the
+// tab_i / tab_p: the natural-order tables [orders][n_mesh][nbp] with the boundary map folded into their rows (wf_model_build.cpp: bc_map; the
 // wave kernels' d_tabI4 / d_tabP3) -- identical to ModelDev's plain ones when the constraints only zero end coefficients
 __global__ void k_prepare_dim0(const ModelDev* __restrict__ mdp, int nm, const float* __restrict__ coef, const float* __restrict__ tab_i,
                                const float* __restrict__ tab_p, f32x4* __restrict__ comp) {
@@ -180,7 +180,7 @@ __global__ void k_pair_dim0(const f32x4* __restrict__ comp, int n_nets, int nm, 
 // pairs in MFMA A-operand order, so the column sum is -0.5 * sum over the 64 k's of (hi + lo).  One thread per bias entry, fixed
 // summation order (deterministic); runs after k_pack at every parameter upload.  Padding rows have zero weights: unchanged.
 // ovf[net] (may be null) = 1 when a packed weight of the net left the fp16 range (|scale * W| >= 65 520: its hi half is +-inf), else 0 -- rewritten at
-// every upload.  The matrix-core kernels would turn such a weight into inf / NaN for every walker; wf_model.cpp routes around them while it is set
+// every upload.  The matrix-core kernels would turn such a weight into inf / NaN for every walker; wf_dispatch.cpp routes around them while it is set
 // (include/waveflow_hip.h: "fp16 range") and k_mfma / k_efused poison their outputs with NaN if they are launched anyway (a captured graph).
 __global__ void k_fold_bias(float* __restrict__ image, int net_floats, int D, int nbk, int* __restrict__ ovf) {
     const int S0 = (D + 1) / 2;
@@ -223,15 +223,13 @@ __global__ void k_fold_bias(float* __restrict__ image, int net_floats, int D, in
 }
 
 int waves_per_group(int tiles, int nbk) {
-    const char* e = getenv("WF_MFMA_WAVES");
-    const int v = e ? atoi(e) : 0;
+    const int v = env_mfma_waves();
     if (tiles == 2) return (v == 4 || v == 8) ? v : 8;
     // (two row blocks per dimension: 0.347 ms at 12 waves, 0.354 at 16, 0.369 at 8 -- scratch/time_waves.py, 33-knot He, 2^20 walkers)
     return (v == 8 || v == 12 || v == 16) ? v : (nbk == 2 ? 12 : 16);
 }
 int tiles_per_wave() {
-    const char* e = getenv("WF_MFMA_TILES");
-    const int v = e ? atoi(e) : 0;
+    const int v = env_mfma_tiles();
     return (v == 1 || v == 2) ? v : 1;
 }
 
@@ -267,7 +265,7 @@ int launch_prepare_dim0(const ModelDev* md_dev, int n_nets, int n_mesh, const fl
                         const float* tab_p_dev, void* comp_dev, void* stream) {
     const int total = n_nets * n_mesh;
     if (total <= 0) return WF_OK;
-    // the coefficient block sits behind the tables in the same allocation (wf_model.cpp reserves dim0_coef_floats)
+    // the coefficient block sits behind the tables in the same allocation (wf_model_images.cpp: mfma_prepare reserves dim0_coef_floats)
     float* coef = reinterpret_cast<float*>(comp_dev) + (size_t)total * 4;
     hipLaunchKernelGGL(k_dim0_coeffs, dim3(n_nets), dim3(64), 0, (hipStream_t)stream, md_dev, fk_nat_dev, F_I, F_P, coef);
     hipLaunchKernelGGL(k_prepare_dim0, dim3((4 * total + 255) / 256), dim3(256), 0, (hipStream_t)stream, md_dev, n_mesh, (const float*)coef,
@@ -307,8 +305,8 @@ int launch_mfma(int D, int nbk, const MfmaDev* mdev, int lds_bytes, int mode, co
             case 7: GO(7, 1, 8);
             case 8:
 #ifdef WF_D8_WAVES_ALL
-                if (waves_per_group(1, 1) == 12 && getenv("WF_MFMA_WAVES")) GO(8, 1, 12);
-                if (waves_per_group(1, 1) == 16 && getenv("WF_MFMA_WAVES")) GO(8, 1, 16);
+                if (waves_per_group(1, 1) == 12 && env_mfma_waves_set()) GO(8, 1, 12);
+                if (waves_per_group(1, 1) == 16 && env_mfma_waves_set()) GO(8, 1, 16);
 #endif
                 GO(8, 1, 8);   // (16 waves: 0.62 ms against 0.45 ms at 2^18 walkers -- register spills)
             default: return WF_ERR_UNSUPPORTED;

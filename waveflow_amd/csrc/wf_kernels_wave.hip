@@ -1474,7 +1474,7 @@ int launch_wave_eval(const ModelDev& md, const ModelDev* md_dev, const float* ta
 // (3 channels each) for every D = 2..8 (scratch/energy_ab.py).  33 .. 64 bases at D >= 5: R3, which fits the registers (second_order_rf).
 int launch_wave_energy(const ModelDev& md, const ModelDev* md_dev, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x,
                        int64_t B, const Protons& pr, float* hpsi, float* psi, float* lap, float* tail_ws, void* stream) {
-    const bool force_r3 = getenv("WF_ENERGY_R3") != nullptr;   // A/B switch, read per call (tests compare the two sweeps)
+    const bool force_r3 = env_energy_r3();   // A/B switch, read per call (tests compare the two sweeps)
     const int kind = (force_r3 || !second_order_rf(md.D, md.nbp)) ? 1 : 3;
     int rc = launch_wave_fwd(md, md_dev, kind, tabI4, tabP4, fk_nat, x, B, nullptr, tail_ws, 0, stream);
     if (rc) return rc;

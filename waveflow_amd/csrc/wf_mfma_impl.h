@@ -297,7 +297,7 @@ constexpr bool kCenter = true;
 #else
 constexpr bool kCenter = false;
 #endif
-// float offsets inside a net image (wf_model.cpp: build_mfma_image); NBK = 32-row blocks per dimension (1 or 2)
+// float offsets inside a net image (wf_model_images.cpp: describe_mfma_image); NBK = 32-row blocks per dimension (1 or 2)
 template <int D, int NBK>
 struct NetOff {
     static constexpr int S0 = (D + 1) / 2;
@@ -418,7 +418,7 @@ __device__ __forceinline__ void out_block_first(const float* net, Frag (&h2)[T][
     mfma_step<T>(W2h, W2l, 1, 1, h2, o, lane);
 }
 
-// tab: [mesh][8 NBK pieces][NO][side: m, m + 1][4 rows] (wf_model.cpp: pack_rows_pairs); rs: [mesh][NO] (read when RS); bnd (LDS):
+// tab: [mesh][8 NBK pieces][NO][side: m, m + 1][4 rows] (wf_model_images.cpp: pack_rows_pairs); rs: [mesh][NO] (read when RS); bnd (LDS):
 // [NBK][half][16: 4 x (lo, hi), 8 unused] support bounds of the lane's pieces (piece_bounds).  One record = both lerp ends and all
 // orders of four rows: a lane reads four records per block, each at the mesh index clamped to the piece's support -- outside it the
 // table holds the bits of the clamped record, so the values are those at the walker's own index, and the walkers outside a piece's
