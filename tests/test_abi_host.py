@@ -159,5 +159,5 @@ def test_environment_switches_live_in_wf_env_h_and_readme_lists_them():
         in_readme |= set(re.findall(r"WF_[A-Z0-9_]+", line.split("|")[1]))
     not_the_library = {"WF_LIB", "WF_LIB_EXPERIMENT", "WF_SKIP_ISA_GUARD", "WF_CXXFLAGS", "WF_GRAPH_COLLECTIVE", "WF_FORCE_DIST"}
     not_the_library |= {n for n in in_readme if n.startswith("WF_BENCH_")}
-    assert len(in_header) >= 20
+    assert len(in_header) == 19
     assert in_header == in_readme - not_the_library, (sorted(in_header - in_readme), sorted(in_readme - not_the_library - in_header))

@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # NaN draws for 2 - 40 % of the walkers, other ones from run to run, the code object byte-identical to a build that had worked.
 # Pre-allocated spill VGPRs end it; every translation unit is built this way (scratch/sgpr_spill_scan.py lists the kernels that spill).
 FLAGS += ["-mllvm", "-amdgpu-prealloc-sgpr-spill-vgprs"]
-FLAGS += os.environ.get("WF_CXXFLAGS", "").split()  # experiment switches (-DWF_...)
+FLAGS += os.environ.get("WF_CXXFLAGS", "").split()  # extra compiler flags (e.g. -save-temps)
 # No packed-FP32 VALU code (v_pk_fma_f32 ...) in the translation units of the MFMA kernels: wf_mfma_impl.h, DESIGN.md §9.  The SLP
 # vectorizer is one source of it, instruction selection of two-element float vectors another (the box transform's differences came out as
 # v_pk_add_f32 in the D >= 3 builds): the target feature is switched off for these units (the host pass does not know the feature and says

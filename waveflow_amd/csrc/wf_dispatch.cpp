@@ -134,9 +134,6 @@ static int dispatch(const wf_model* m, int mode, const float* x, int64_t B, floa
         if (m->kernel_kind == WF_KERNEL_MFMA) return WF_ERR_UNSUPPORTED;
         use_mfma = false;
     }
-#if defined(WF_DEBUG) || defined(WF_STAMP)
-    if (use_mfma) (void)env_dbg_ptr(&const_cast<wf_model*>(m)->mdev.dbg);
-#endif
     if (use_mfma)
         return launch_mfma(m->dev.D, m->mdev.nbk, &m->mdev, (int)(m->mfma_lds_floats * sizeof(float)), mode | (presort ? kModePresort : 0), x, B, out, u, idx, stream);
     int32_t* inv = nullptr;

@@ -54,7 +54,6 @@ inline bool env_sample_one_lane() { return env_set("WF_SAMPLE_ONE_LANE"); }
 inline bool env_sample_group_phase2() { return env_set("WF_SAMPLE_GROUP_PHASE2"); }
 // workgroup shape of k_mfma (at every launch): the value as a number, 0 when unset; the launcher accepts the shapes it was built with
 inline int env_mfma_waves() { return env_int("WF_MFMA_WAVES", 0); }
-inline bool env_mfma_waves_set() { return env_set("WF_MFMA_WAVES"); }
 inline int env_mfma_tiles() { return env_int("WF_MFMA_TILES", 0); }
 // per call by the energy sweep, at model creation for the gradients (second_order_rf, wf_internal.h)
 inline bool env_wide_rf() { return env_set("WF_WIDE_RF"); }
@@ -66,14 +65,5 @@ inline bool env_prior_quotient() { return env_int("WF_PRIOR_QUOTIENT", 0) != 0; 
 
 // ---- at every device allocation of a model
 inline bool env_poison() { return env_set("WF_POISON"); }
-
-#if defined(WF_DEBUG) || defined(WF_STAMP)
-// diagnostics builds only (per call): device address of the stamp / debug buffer of k_mfma, strtoull with base 0; false when unset
-inline bool env_dbg_ptr(float** out) {
-    const char* e = env_raw("WF_DBG_PTR");
-    if (e) *out = (float*)strtoull(e, nullptr, 0);
-    return e != nullptr;
-}
-#endif
 
 }  // namespace wf

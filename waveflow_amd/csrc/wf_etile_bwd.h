@@ -41,11 +41,7 @@ __device__ __forceinline__ float wave_max(float v) {   // v >= 0
 __device__ __forceinline__ int exponent_of(float amax) { return amax > 0.0f ? __builtin_amdgcn_frexp_expf(amax) : 0; }
 using JA = adj::Jt<float>;
 using TA = adj::T2t<float>;
-#ifndef WF_BWD_WAVES
-#define WF_BWD_WAVES 4
-#endif
-#define WF_BWD_WAVES_ WF_BWD_WAVES
-constexpr int kBwdWaves = WF_BWD_WAVES;
+constexpr int kBwdWaves = 4;
 // Gradient block of a net (floats, in the units of the MFMA image; NBK = 32-row blocks of the head per dimension):
 //   GW0 [64] (d / d W0'[0][u]), Gb0 [64], GW1 [64][64] (k, u), Gb1 [64], GW2 [64][32 NBK] (k, row), Gb2 of dimension 1 [32 NBK], of dimension 0 [32 NBK]
 template <int NBK>
@@ -59,14 +55,10 @@ constexpr int kESplit = 256;        // partial blocks per net: one per workgroup
 // each [4 q][64 lanes][4] (register 4 q + e of the lane: one conflict-free ds_read_b128 per q)
 constexpr int acc_blocks(int nbk) { return 4 + 2 * nbk; }
 // sets of accumulator blocks per workgroup.  One row block: a private set per wave (4 x 24 KB beside 66 KB of images), summed in wave order at the end.
-// Two row blocks: the four private sets (128 KB) do not fit beside 103 KB of images -- ONE shared set filled in tile order (acc_add).  -DWF_ACC_SHARED
-// (experiment) shares the set for one row block too: 1.040 ms per loss + gradient of 2^17 walkers against 0.985 ms (the waves move in step, one add apart:
+// Two row blocks: the four private sets (128 KB) do not fit beside 103 KB of images -- ONE shared set filled in tile order (acc_add).  Sharing
+// the set for one row block too was measured: 1.040 ms per loss + gradient of 2^17 walkers against 0.985 ms (the waves move in step, one add apart:
 // any jitter of one holds up the other three); profiles/r04_grad33_times.txt
-#ifdef WF_ACC_SHARED
-constexpr int acc_sets(int) { return 1; }
-#else
-constexpr int acc_sets(int nbk) { return nbk == 1 ? WF_BWD_WAVES_ : 1; }
-#endif
+constexpr int acc_sets(int nbk) { return nbk == 1 ? kBwdWaves : 1; }
 __device__ __forceinline__ int acc_rho(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // row of register r in lane half h (accumulator layout)
 __device__ __forceinline__ f32x16 acc_load(const float* aw, int b, int lane) {
     f32x16 a;
@@ -498,13 +490,8 @@ __device__ __forceinline__ void wgrad_block(f32x16& p, const Frag& xt, const Fra
 // block is therefore formed in the same order whatever the timing (bitwise reproducible gradients) although the waves share ONE set of blocks.  Progress:
 // tile k waits only for tile k - 1's wave to pass the same point, tile 0 for nobody; the waves of a workgroup are resident together and each works
 // through its tiles in increasing k, so every wait ends (the waves fall into step one add apart: ~200 cycles in a tile of ~10^5).
-template <bool SHARED_>
+template <bool SHARED>
 __device__ __forceinline__ void acc_add(float* acc, int* ticket, int b, int k, int lane, const f32x16& p, float un) {
-#ifdef WF_ACC_NOTICKET   // timing experiment only (racy sums): what the tile order costs
-    constexpr bool SHARED = false;
-#else
-    constexpr bool SHARED = SHARED_;
-#endif
     if (SHARED) {
         // Nothing of the matrix pipe may be in flight across the branch of the wait below.  hipcc (ROCm 7.2) counts the wait states between an MFMA and a
         // vector read of its result correctly in straight-line code, but at the join behind this loop it let v_accvgpr_read follow the product's last
@@ -526,12 +513,6 @@ __device__ __forceinline__ void acc_add(float* acc, int* ticket, int b, int k, i
 }  // namespace
 // (k_ebwd has external linkage: its two-row-block instantiations are compiled in a translation unit of their own, wf_etile_bwd_k2.hip, under the
 // max-ilp scheduling strategy, which is worth 6 % to them and costs the one-row-block form 1 %: DESIGN 4.9)
-// -DWF_MARKS: comment lines in the assembly at the phase boundaries of k_ebwd (scratch/r04_spill_phases.py counts the spill traffic per phase)
-#ifdef WF_MARKS
-#define WF_MARK(name) asm volatile("; WF_MARK " name)
-#else
-#define WF_MARK(name)
-#endif
 template <bool PRIOR, int NBK>
 __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int net_index, const float* __restrict__ tabI, const float* __restrict__ tabP,
                                                           const float* __restrict__ st_in, float* __restrict__ adjb, const float* __restrict__ w_psi,
@@ -628,7 +609,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
         const int64_t wl = valid ? w : B - 1;
         // (padding lanes of the last tile repeat walker B - 1 with zero adjoints: their columns add nothing to the sums over walkers)
         const JA u0 = ja_load(st_in, 0, B, wl), u1 = ja_load(st_in, 1, B, wl);
-        WF_MARK("tile_start");
         // ---- the net's forward to the head triples o.  The second hidden layer's pre-activations z2, which the reverse needs, are computed again
         // behind the head: 96 registers less across the head algebra
         f32x16 o[NBK][NCH];
@@ -636,7 +616,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
             f32x16 z2a[NCH], z2b[NCH];
             cond_fwd<true, NBK>(net, u0.v, u1.v, lane, z2a, z2b, o);
         }
-        WF_MARK("fwd_done");
         // ---- head: forward sums, pullback to adjoint head triples ob (dimension 1) and ob0 (dimension 0, channel 0)
         f32x16 ob[NBK][NCH], ob0[NBK];
         JA u0b = adj::jzero<float>(), u1b = adj::jzero<float>(), ldb = adj::jzero<float>();
@@ -819,7 +798,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
                 }
             }
         }
-        WF_MARK("head_done");
         // Gb2 of dimension 0: sum over the tile's walkers of obar0 (16 registers per half: DPP sums; lane (j, h) keeps register j & 15 where j < 16)
 #pragma unroll
         for (int kb = 0; kb < NBK; ++kb) {
@@ -841,7 +819,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
             f32x16 o2[NBK][NCH];
             cond_fwd<false, NBK>(net, u0.v, u1.v, lane, z2a, z2b, o2);
         }
-        WF_MARK("refwd_done");
         // dW2[k][row] = sum_c sum_w X2_c[k][w] obar_c[row][w]: X2 = act(z2), block by block (32 units: 48 registers of fragments at a time); both operands
         // transposed on the matrix cores; the 2 x NBK blocks of the product go to the accumulator blocks 4 + (k block) NBK + (row block).  Gb2 rides on
         // obar's transposes.
@@ -876,7 +853,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
                 for (int kb = 0; kb < NBK; ++kb) acc_add<kShared>(acc, ticket, 4 + mb * NBK + kb, k, lane, p[kb], __builtin_amdgcn_ldexpf(1.0f, E));
             }
         }
-        WF_MARK("dW2_done");
         f32x16 g0[NCH], g1[NCH];
         {
 #pragma unroll
@@ -893,7 +869,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
             act_block_bwd(z2a, g0);
             act_block_bwd(z2b, g1);
             to_frags_all<true>(g0, g1, f, e);
-            WF_MARK("zbar2_done");
             // dW1[k][u] = sum_c sum_w X1_c[k][w] zbar2_c[u][w] while the fragments of zbar2 (f, exponents e) are at hand and before the product that
             // consumes them: X1, the first hidden layer's activation triples, is recomputed block by block from (s, 1, 0) (two f32 MFMAs and 16
             // activations per lane and block).  Accumulator blocks 0 .. 3 = (k block mb, u block nb); Gb1 rides on the transposes of zbar2.
@@ -929,7 +904,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
                     }
                 }
             }
-            WF_MARK("dW1_done");
 #pragma unroll
             for (int c = 0; c < NCH; ++c) { g0[c] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; g1[c] = g0[c]; }
             dense64_block<NCH>(TW1h, TW1l, f, g0, lane);
@@ -973,7 +947,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_ebwd(const MfmaDev mm, int n
             for (int r = 0; r < 16; ++r) sbar = __builtin_fmaf(wa[r], g0[0][r], __builtin_fmaf(wb2[r], g1[0][r], sbar));
             u0b.v += xhalf_sum(sbar);
         }
-        WF_MARK("tile_end");
         if (valid && h == 0) {
             ja_store(adjb, 0, B, w, u0b);
             ja_store(adjb, 1, B, w, u1b);

@@ -8,13 +8,8 @@
 namespace wf {
 namespace {
 
-#ifndef WF_ETILE_WAVES
-#define WF_ETILE_WAVES 4
-#endif
-#ifndef WF_ETILE_OCC
-#define WF_ETILE_OCC 2   // workgroups per CU the register budget is sized for: 256 registers, two waves per SIMD (the per-lane store addresses spill: 23 reloads per tile)
-#endif
-constexpr int kCondWaves = WF_ETILE_WAVES;   // 4 waves per workgroup, WF_ETILE_OCC workgroups per CU (unbounded, the three channel chains take 324 registers: one wave per SIMD)
+constexpr int kCondWaves = 4;   // waves per workgroup, kCondOcc workgroups per CU (unbounded, the three channel chains take 324 registers: one wave per SIMD)
+constexpr int kCondOcc = 2;     // workgroups per CU the register budget is sized for: 256 registers, two waves per SIMD (the per-lane store addresses spill: 23 reloads per tile)
 // r(x) = 1 / (2^x + 1), the activation of the MFMA images, on a value alone (the reverse helpers of wf_etile_bwd.h, the heads of the staged sampler)
 __device__ __forceinline__ float r_of(float x) { return __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x) + 1.0f); }
 
@@ -106,7 +101,7 @@ __device__ __forceinline__ void cond_net(const float* net, const float* fkP, con
 // CH = 1 (the staged sampler: round 4): the value channel alone -- a third of the matrix products, no derivative algebra in the activations, 128 instead of
 // 384 B per walker and row block out (oj[tile][row][32 walkers])
 template <bool PRIOR, int NBK = 1, int CH = NCH>
-__global__ __launch_bounds__(kCondWaves * 64, WF_ETILE_OCC) void k_etile_cond(const MfmaDev mm, int net_index, const float* __restrict__ st, int64_t B,
+__global__ __launch_bounds__(kCondWaves * 64, kCondOcc) void k_etile_cond(const MfmaDev mm, int net_index, const float* __restrict__ st, int64_t B,
                                                                 float* __restrict__ oj, float* __restrict__ s1buf, float* __restrict__ ow = nullptr) {
     // ow (PRIOR, CH = 1; may be null): the value channel of o * keep, [tile][row][32 walkers] -- where the boundary map only zeroes coefficients these ARE the
     // plain B-spline coefficients of c (c = (o keep) @ ob_to_b, and ob_to_b @ b_to_ob = 1): the staged sampler's envelope reads them instead of forming c @ b_to_ob
@@ -147,11 +142,7 @@ __global__ __launch_bounds__(kCondWaves * 64, WF_ETILE_OCC) void k_etile_cond(co
                 for (int r = 0; r < 16; ++r) ow[(tile * (32 * NBK) + 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h) * 32 + j] = wk[kb][r];
         }
         // ---- store: oj[tile][row][c][32 walkers] (one contiguous block per tile), row = accumulator row of register r in lane half h of block kb
-#ifdef WF_ABL_OJ   // ablation build (timing only): the head triples are computed, not stored
-        if (valid && a0[0][0][0] == 12345.678f) {
-#else
         if (valid) {
-#endif
 #pragma unroll
             for (int kb = 0; kb < NBK; ++kb)
 #pragma unroll

@@ -117,7 +117,7 @@ struct MfmaDev {
     const float* tabP;         // [n_mesh][8 nbk pieces][side][4 rows] fp32, prior rows (B as is; M: fk_row * M_row), nd 0
     const float4_t* comp;      // [n_nets][n_mesh] composite tables of output dimension 0 (k_prepare_dim0)
     const float4_t* comp2;     // [n_nets][n_mesh]{comp[m].xy, comp[m + 1].xy}: both lerp ends of what k_mfma reads, one 16-byte record (k_pair_dim0)
-    float* dbg;                // diagnostics builds only (WF_DEBUG / WF_STAMP)
+    float* reserved_ptr;       // reserved: never read, always null (it keeps the kernarg offsets of the fields behind it)
     int exact_div;             // 1: x_l / n by IEEE division (set when the multiply-and-correct form is not bit-identical for this n_mesh)
     int prior_quotient;        // debug (env WF_PRIOR_QUOTIENT=1 at model creation): Waveflow prior head in the reference's quotient form
     int i_gate, p_gate;        // gated heads (wf_model_desc.i_gate / p_gate): zero_params blocks of the net images are live
@@ -179,13 +179,7 @@ int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tab
 // The taped sweeps use kind 2 with K = D up to 5 coordinates; beyond, the 8..10 live floats per value of RF<D> spill hundreds of registers
 // in the reverse sweep and two blocks of 3 or 4 directions are ~20 % faster.  The untaped forward sweep of wf_hamiltonian_fwd is fastest
 // with the whole walker in one sample (kind 3) for every D (scratch/energy_ab.py, scratch/grad_ab.py).
-#ifndef WF_RF_BLOCK_6
-#define WF_RF_BLOCK_6 3
-#endif
-#ifndef WF_RF_BLOCK_78
-#define WF_RF_BLOCK_78 4
-#endif
-constexpr int rf_block(int D) { return D <= 5 ? D : (D == 6 ? WF_RF_BLOCK_6 : WF_RF_BLOCK_78); }
+constexpr int rf_block(int D) { return D <= 5 ? D : (D == 6 ? 3 : 4); }
 inline int ring_coefs(int D, int kind) { return kind == 0 ? 1 : (kind == 1 ? 3 : (kind == 2 ? rf_block(D) + 2 : D + 2)); }
 inline int ring_samples(int D, int kind) { return (kind == 0 || kind == 3) ? 1 : (kind == 1 ? D : (D + rf_block(D) - 1) / rf_block(D)); }
 // The second-order sweeps of 33 .. 64 bases (one dimension x 64 rows per pass) fit RF up to D = 4 only: for D = 5 .. 8 the RF forms keep

@@ -100,11 +100,7 @@ __device__ __forceinline__ float rows_lerp(const float* __restrict__ tab0, const
     const float4_t* ra = reinterpret_cast<const float4_t*>(tab0 + (size_t)L.il * NB);
     const float4_t* rb = reinterpret_cast<const float4_t*>(tab0 + (size_t)L.ir * NB);
     float acc = 0.0f;
-#ifdef WF_TS_FAKE_BAND   // timing experiment only (wrong values): three of the NB / 4 records per row, as a band-limited evaluation would read
-    constexpr int kQ = 3;
-#else
     constexpr int kQ = NB / 4;
-#endif
 #pragma unroll
     for (int q = 0; q < kQ; ++q) {
         const float4_t a = ra[q], b = rb[q];
@@ -338,11 +334,10 @@ __global__ __launch_bounds__(256, 2) void k_tsample(const TsArgs a, int layer, c
         // Stage A: every lane proposes for its own walker, kTsOwn times at most (88 % of the walkers are done by then).  Stage B: the wave's remaining
         // walkers get eight lanes each, eight consecutive proposals of a walker's sequence per round, the first accepted one in sequence order taken --
         // the same draws as one lane proposing on alone, without the wave waiting 80 rounds for its unluckiest lane.
-#ifndef WF_TS_OWN   // (experiment switch; the draws do not depend on it.  2^17 draws, round 4: 16 own proposals 0.281 ms, 12: 0.283, 8: 0.287, 4: 0.294)
-#define WF_TS_OWN 16
-#endif
-        constexpr int kTsOwn = WF_TS_OWN;
-        int n_prop = 0;
+        constexpr int kTsOwn = 16;   // (the draws do not depend on it.  2^17 draws, round 4: 16 own proposals 0.281 ms, 12: 0.283, 8: 0.287, 4: 0.294)
+        // n_prop (with rounds / rmine below): the walker's number of proposals, which nothing reads any more.  Without them hipcc's code for
+        // k_tsample<1, 32> differs (142 spilled SGPRs instead of 140), so they go in a change of their own that is measured on the GPU.
+        [[maybe_unused]] int n_prop = 0;
         float xs = __builtin_nanf("");
         bool done = false;
         const unsigned long long wb_own = (unsigned long long)(a.b0 + b);
@@ -396,14 +391,7 @@ __global__ __launch_bounds__(256, 2) void k_tsample(const TsArgs a, int layer, c
             }
         }
         const float l0 = lat[b];
-#ifdef WF_TS_COUNT   // diagnostics build: the number of proposals of column 1 instead of its draw in the reported latent
-        if (latent_out) { latent_out[b * 2] = l0; latent_out[b * 2 + 1] = (float)n_prop; }
-#else
         if (latent_out) { latent_out[b * 2] = l0; latent_out[b * 2 + 1] = xs; }
-#endif
-#ifdef WF_TS_DEBUG   // (diagnostics: an intermediate instead of the first column in the reported latent)
-        if (latent_out) latent_out[b * 2] = WF_TS_DEBUG == 1 ? tot : (WF_TS_DEBUG == 2 ? rn : msq[WF_TS_DEBUG - 3]);
-#endif
         start_layer(a.n_layers - 1, l0, xs);
         return;
     }
@@ -545,9 +533,6 @@ __global__ __launch_bounds__(256) void k_tsample_p1g(const TsArgs a, const float
     if (valid && r == 0) {
         const float l0 = lat[b];
         if (latent_out) { latent_out[b * 2] = l0; latent_out[b * 2 + 1] = xw; }
-#ifdef WF_TS_DEBUG
-        if (latent_out) latent_out[b * 2] = WF_TS_DEBUG == 1 ? tot : (WF_TS_DEBUG == 2 ? rn : mq[WF_TS_DEBUG - 3]);
-#endif
         // the last layer's dimension 0 from the pair that leaves the prior (k_tsample: start_layer)
         const int l = a.n_layers - 1;
         const float o0 = inv_comp(a.comp + (size_t)l * n_mesh, n_mesh, xw, a.tol);

@@ -30,24 +30,11 @@ namespace {
 using namespace ring;
 constexpr int H = kHidden;
 constexpr int kWaves = 4;
-// waves per SIMD the register allocation of each kernel family aims at (measured: DESIGN.md §4.5, scratch/occ_try.sh)
-#ifndef WF_OCC_FWD1
-#define WF_OCC_FWD1 3   // k_wave_fwd<D, R1>
-#endif
-#ifndef WF_OCC_FWD2
-#define WF_OCC_FWD2 3   // k_wave_fwd<D, R3 / RF>
-#endif
-#ifndef WF_OCC_BWD1
-#define WF_OCC_BWD1 3   // k_wave_bwd<D, R1>
-#endif
-#ifndef WF_OCC_BWD2
-#define WF_OCC_BWD2 2   // k_wave_bwd<D, R3 / RF>: 256 registers per lane (RF<2>: 1.92e7 -> 2.31e7 walkers/s, batch 128: 86 -> 60 us)
-#endif
-#ifndef WF_OCC_SAMPLE
-#define WF_OCC_SAMPLE 3
-#endif
-template <class T> constexpr int kOccFwd = T::NC == 1 ? WF_OCC_FWD1 : WF_OCC_FWD2;
-template <class T> constexpr int kOccBwd = T::NC == 1 ? WF_OCC_BWD1 : WF_OCC_BWD2;
+// waves per SIMD the register allocation of each kernel family aims at (measured: DESIGN.md §4.5)
+template <class T> constexpr int kOccFwd = 3;                      // k_wave_fwd<D, R1> and k_wave_fwd<D, R3 / RF>
+// k_wave_bwd<D, R1>: 3; k_wave_bwd<D, R3 / RF>: 2 = 256 registers per lane (RF<2>: 1.92e7 -> 2.31e7 walkers/s, batch 128: 86 -> 60 us)
+template <class T> constexpr int kOccBwd = T::NC == 1 ? 3 : 2;
+constexpr int kOccSample = 3;                                      // k_wave_sample
 constexpr int kWB = 64 * kWaves;
 
 // ---- coefficient access
@@ -135,9 +122,6 @@ template <class T> __device__ __forceinline__ void put(float (*buf)[64], int lan
 // out[lane] = sum_a in[a] * W[lane][a], W in lane-major float4 groups.  Even and odd a accumulate in the two halves of a
 // packed pair (v_pk_fma_f32: two FMAs per lane and instruction) and are added at the end.
 using float2_t = __attribute__((ext_vector_type(2))) float;
-#ifndef WF_GEMV_UNROLL_BWD
-#define WF_GEMV_UNROLL_BWD 4
-#endif
 template <class T, bool PRELOAD = false, int UNROLL = 4>
 __device__ __forceinline__ T gemv(const float4_t* __restrict__ img, const float (*buf)[64], int lane) {
     float2_t acc[T::NC];
@@ -689,7 +673,7 @@ __device__ __forceinline__ void hidden_bwd(const NetWave& net, T hb2, float (*ve
     const T A2 = hb2 * (1.0f - h2 * h2);
     tput(tape, n, Rows<D>::A2 + lane, A2);
     put(vec, lane, A2);
-    const T hb1 = gemv<T, false, WF_GEMV_UNROLL_BWD>(net.W1b, vec, lane);
+    const T hb1 = gemv<T>(net.W1b, vec, lane);
     const T h1 = tget<T>(tape, n, Rows<D>::H1 + lane);
     const T A1 = hb1 * (1.0f - h1 * h1);
     tput(tape, n, Rows<D>::A1 + lane, A1);
@@ -868,7 +852,7 @@ __global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(kOccBwd<T>,
                 }
                 if (valid_d) tput(tape, NP, RW::O + d * W + j, go);
                 put(ov, lane, go);
-                hb2 = hb2 + gemv<T, false, WF_GEMV_UNROLL_BWD>(net.W2b + p * 1024, ov, lane);
+                hb2 = hb2 + gemv<T>(net.W2b + p * 1024, ov, lane);
             }
             hidden_bwd<D, T>(net, hb2, vec, lane, tape, NP, gU);
             if (gate_p) {   // the gates see the conditioner's input: the unclipped u
@@ -954,7 +938,7 @@ __global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(kOccBwd<T>,
                 }
                 if (valid_d) tput(tape, l, RW::O + d * W + j, go);
                 put(ov, lane, go);
-                hb2 = hb2 + gemv<T, false, WF_GEMV_UNROLL_BWD>(net.W2b + p * 1024, ov, lane);
+                hb2 = hb2 + gemv<T>(net.W2b + p * 1024, ov, lane);
             }
             hidden_bwd<D, T>(net, hb2, vec, lane, tape, l, gU);
             if (gate_i) {
@@ -1146,7 +1130,7 @@ __device__ __forceinline__ void wave_serial_inverse(const ModelDev& md, const fl
 
 // seed_mode 0: invert the latent points ug;  1: draw the latent points from the prior first (and report them)
 template <int D, int NBK = 1>
-__global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(WF_OCC_SAMPLE, WF_OCC_SAMPLE))) void k_wave_sample(
+__global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(kOccSample, kOccSample))) void k_wave_sample(
     const ModelDev* __restrict__ mdp, const float* __restrict__ tabI, const float* __restrict__ tabP, const float* __restrict__ fk_nat, int draw,
     unsigned long long seed, const float* __restrict__ ug, int64_t B, float* __restrict__ xg, float* __restrict__ latent, int exact,
     const unsigned long long* __restrict__ seed_offset_dev) {

@@ -13,23 +13,9 @@
 
 #include "wf_internal.h"
 
-// the loops over a net's output dimensions: unrolled (kDimUnroll<D> = D).  -DWF_D8_ROLLED (experiment, round 4) rolls them for the long chains (D > 4):
-// no spilled registers at 8 waves instead of 10, 75 / 207 at 12 / 16 waves instead of 172 / 346 -- and 2 - 5 % SLOWER at 8 waves (D = 8, 2^18 walkers:
-// 0.319 against 0.314 ms), 12 and 16 waves slower still (0.365 / 0.472 ms): profiles/r04_c4_rolled_loops_and_waves.txt.  Same bits either way.
-template <int D>
-#ifdef WF_D8_ROLLED
-constexpr int kDimUnroll = D > 4 ? 1 : D;
-#else
-constexpr int kDimUnroll = D;
-#endif
-
 // WF_PIN(): keeps the hand-written order of [MFMA K step | activation of another block] units (hidden_layers, out_block_first): the
 // scheduler is free inside a unit, not across units.
-#ifdef WF_NO_PIN
-#define WF_PIN()
-#else
 #define WF_PIN() __builtin_amdgcn_sched_barrier(0)
-#endif
 
 namespace wf {
 namespace mfma {
@@ -40,46 +26,16 @@ using i32x2 = __attribute__((ext_vector_type(2))) int;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
-// Experiment builds (scratch/r04_parity_variants.py; timing is irrelevant there): one class of hardware approximations at a time replaced by fp64
-// arithmetic, to attribute the kernel's deviation from the reference -- WF_X_ACT: hidden activations, WF_X_SIG: sigmoid heads, WF_X_LOG: logarithms,
-// WF_X_RCP: reciprocals / reciprocal square roots of the heads.
-__device__ __forceinline__ float x_rinv(float xs) {   // 1 / (2^xs + 1)
-#if defined(WF_X_ACT) || defined(WF_X_SIG)
-    return (float)(1.0 / (exp2((double)xs) + 1.0));
-#else
-    return __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(xs) + 1.0f);
-#endif
-}
-__device__ __forceinline__ float x_rcp(float v) {
-#ifdef WF_X_RCP
-    return (float)(1.0 / (double)v);
-#else
-    return __builtin_amdgcn_rcpf(v);
-#endif
-}
-__device__ __forceinline__ float x_rsq(float v) {
-#ifdef WF_X_RCP
-    return (float)(1.0 / sqrt((double)v));
-#else
-    return __builtin_amdgcn_rsqf(v);
-#endif
-}
+// The transcendentals are the hardware approximations (v_exp_f32, v_rcp_f32, v_rsq_f32, v_log_f32).  What each class of them contributes to the
+// kernel's deviation from the reference was measured with one class at a time replaced by fp64 arithmetic: DESIGN.md section 6.
 __device__ __forceinline__ float act_tanh(float xs) {  // xs = 2*log2(e)*x (scale folded into the weights)
     return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(xs) + 1.0f), 1.0f);
 }
 __device__ __forceinline__ float act_sigmoid(float xs) {  // xs = -log2(e)*x
-#ifdef WF_X_SIG
-    return x_rinv(xs);
-#else
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(xs));
-#endif
 }
 __device__ __forceinline__ float fast_log(float x) {
-#ifdef WF_X_LOG
-    return (float)log((double)x);
-#else
     return __builtin_amdgcn_logf(x) * 0.6931471805599453f;
-#endif
 }
 
 // sum of the two lane halves (lane l and l^32), result in every lane
@@ -89,22 +45,7 @@ __device__ __forceinline__ float xhalf_sum(float v) {
     return __uint_as_float(s[0]) + __uint_as_float(s[1]);
 }
 
-#ifdef WF_ABL_TAB   // ablation build (timing only): no table loads
-__device__ __forceinline__ f32x16 load16g(const float* p) {
-    const float c = (float)(size_t)p * 1e-20f;
-    return f32x16{c, c, c, c, c, c, c, c, c, c, c, c, c, c, c, c};
-}
-#else
-#define load16g load16
-#endif
-#ifdef WF_ABL_TAB
-__device__ __forceinline__ f32x4 load4g(const float* p) {
-    const float c = (float)(size_t)p * 1e-20f;
-    return f32x4{c, c, c, c};
-}
-#else
-__device__ __forceinline__ f32x4 load4g(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-#endif
+__device__ __forceinline__ f32x4 load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // a wave-uniform float into a scalar register (the builtin is folded away when the compiler knows the value to be uniform, and the value stays in a vector register)
 __device__ __forceinline__ float uniform_f(float v) {
     float r;
@@ -195,18 +136,6 @@ struct Frag {
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 __device__ __forceinline__ void split8(const float (&r)[8], f16x8& hi, f16x8& lo) {
-#ifdef WF_SPLIT_TRUNC
-    // experiment: hi = the value truncated to 11 significant bits (exact in fp16 above 2^-14), lo = rn16(r - hi): v_and + v_sub + two
-    // v_cvt_pk per pair = 3 instructions per value, none of them on the transcendental / mixed-precision rate
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const float h0 = __uint_as_float(__float_as_uint(r[j]) & 0xFFFFE000u), h1 = __uint_as_float(__float_as_uint(r[j + 1]) & 0xFFFFE000u);
-        const f16x2 Hh = __builtin_convertvector((f32x2){h0, h1}, f16x2);
-        const f16x2 Ll = __builtin_convertvector((f32x2){r[j] - h0, r[j + 1] - h1}, f16x2);
-        hi[j] = Hh[0]; hi[j + 1] = Hh[1]; lo[j] = Ll[0]; lo[j + 1] = Ll[1];
-    }
-    return;
-#endif
     u32x4 H, L;
     asm volatile(
         "s_nop 0\n\t"
@@ -232,27 +161,12 @@ template <int T>
 __device__ __forceinline__ void mfma_step(const _Float16* Wh, const _Float16* Wl, int kt, int s, const Frag (&in)[T][2], f32x16 (&acc)[T], int lane) {
     const f16x8 ah = *reinterpret_cast<const f16x8*>(Wh + ((kt * 2 + s) * 64 + lane) * 8);
     const f16x8 al = *reinterpret_cast<const f16x8*>(Wl + ((kt * 2 + s) * 64 + lane) * 8);
-#ifdef WF_ABL_MFMA   // ablation build (timing only): operands stay live, no matrix instructions
-#pragma unroll
-    for (int t = 0; t < T; ++t) asm volatile("" : "+v"(acc[t]) : "v"(ah), "v"(al), "v"(in[t][kt].hi[s]), "v"(in[t][kt].lo[s]));
-    return;
-#endif
-#ifdef WF_SETPRIO
-    __builtin_amdgcn_s_setprio(WF_SETPRIO);
-#endif
-#ifdef WF_MFMA_4PROD   // experiment: the lo * lo term as well (2^-24 relative)
-#pragma unroll
-    for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, in[t][kt].lo[s], acc[t], 0, 0, 0);
-#endif
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, in[t][kt].hi[s], acc[t], 0, 0, 0);
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, in[t][kt].lo[s], acc[t], 0, 0, 0);
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, in[t][kt].hi[s], acc[t], 0, 0, 0);
-#ifdef WF_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 }
 template <int T>
 __device__ __forceinline__ void dense64_block(const _Float16* Wh, const _Float16* Wl, const Frag (&in)[T][2], f32x16 (&acc)[T], int lane) {
@@ -263,40 +177,17 @@ __device__ __forceinline__ void dense64_block(const _Float16* Wh, const _Float16
 }
 // the activation of registers 8s .. 8s+7 of a block (one K = 16 fragment) of every tile: the unit of work that is placed between
 // the K steps of an MFMA chain that does not depend on it (hidden_layers, out_block_first)
-// CENTER: r - 1/2 instead of r (= -tanh / 2: the layer behind takes the UNFOLDED bias NetOff::b1c, see hidden_layers)
-template <int T, bool CENTER = false>
+template <int T>
 __device__ __forceinline__ void act8(const f32x16 (&x)[T], int s, Frag (&f)[T][2], int ob) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-#ifdef WF_ABL_ACT
-        f32x4 a = {x[t][8 * s], x[t][8 * s + 1], x[t][8 * s + 2], x[t][8 * s + 3]}, b = {x[t][8 * s + 4], x[t][8 * s + 5], x[t][8 * s + 6], x[t][8 * s + 7]};
-        f[t][ob].hi[s] = __builtin_bit_cast(f16x8, a);
-        f[t][ob].lo[s] = __builtin_bit_cast(f16x8, b);
-#else
         float r[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-#ifdef WF_X_ACT
-            r[j] = CENTER ? (float)(1.0 / (exp2((double)x[t][8 * s + j]) + 1.0) - 0.5) : x_rinv(x[t][8 * s + j]);
-#else
-            r[j] = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x[t][8 * s + j]) + 1.0f);
-            if (CENTER) r[j] = r[j] - 0.5f;
-#endif
-        }
+        for (int j = 0; j < 8; ++j) r[j] = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x[t][8 * s + j]) + 1.0f);
         split8(r, f[t][ob].hi[s], f[t][ob].lo[s]);
-#endif
     }
 }
 
-// WF_CENTER (experiment build, round 4): the flow nets' first hidden layer hands r - 1/2 to the second one (hidden_layers<..., CENTER>).  The CPU
-// emulation of the kernel's matrix arithmetic (scratch/r04_parity_attribution.py) named that product as the one that moves walkers; on the GPU the
-// centred form changed nothing that can be measured (direct agreement with the fp32 oracle on C3's well-conditioned subset 0.935 against 0.940,
-// profiles/r04_parity_variants_gpu.txt) at + 0.6 % time: not adopted, the switch and the unfolded bias (NetOff::b1c) stay for the record.
-#ifdef WF_CENTER
-constexpr bool kCenter = true;
-#else
-constexpr bool kCenter = false;
-#endif
 // float offsets inside a net image (wf_model_images.cpp: describe_mfma_image); NBK = 32-row blocks per dimension (1 or 2)
 template <int D, int NBK>
 struct NetOff {
@@ -310,8 +201,11 @@ struct NetOff {
     static constexpr int W2l = W2h + (D - 1) * NBK * 1024;
     static constexpr int b2 = W2l + (D - 1) * NBK * 1024;
     static constexpr int z = b2 + 32 * D * NBK;     // zero_params of a gated head [D][NBK][2][16] (zeros otherwise)
-    static constexpr int b1c = z + 32 * D * NBK;    // the second hidden layer's bias WITHOUT the column sums of k_fold_bias [2][2][16] (centred activations)
-    static constexpr int total = b1c + 64;
+    // reserved tail, 64 floats, read by no kernel: the host still writes the second hidden layer's bias WITHOUT the column sums of k_fold_bias there
+    // ([2][2][16]; a centred first-layer activation r - 1/2 took it: measured, not adopted).  It stays because `total` sets a net's
+    // LDS footprint and with it the resident / staged decision.
+    static constexpr int reserved = z + 32 * D * NBK;
+    static constexpr int total = reserved + 64;
 };
 
 // Hidden layers of one conditioner net for the wave's T tiles of 32 walkers.  Written in the order the instructions should issue:
@@ -320,12 +214,11 @@ struct NetOff {
 //   chain(layer 2, block 1)                              ||  activation of layer-2 block 0
 // Result: h2[t][0] complete, pend[t] = pre-activations of layer-2 block 1 (their activation goes under the first K steps of the
 // output chain: out_block_first).
-// CENTER (experiment, -DWF_CENTER; see kCenter): the first hidden layer hands r - 1/2 = -tanh/2 to the second one, whose bias is then the plain
-// c b1 (NetOff::b1c) instead of c (b1 + sum_k W1_k).  With r itself the products (-2 c W1_k) r_k are of the size of the weights while their sum,
-// after the constant cancels, is of the size of sum_k W1_k tanh_k; in a CPU emulation of the matrix arithmetic alone that showed (1.8 % of the
-// well-conditioned walkers moved by more than 1e-5 relative through this product, a fourth product lo * lo changing nothing, the centred form
-// 0.25 - 0.7 %: profiles/r04_parity_attribution_cpu.txt); in the real kernel it is below the fp32 roundings of everything else.
-template <int D, int NBK, int T, bool CENTER = false>
+// (With r itself the products (-2 c W1_k) r_k of the second layer are of the size of the weights while their sum, after the constant cancels, is
+// of the size of sum_k W1_k tanh_k; in a CPU emulation of the matrix arithmetic alone that showed (1.8 % of the well-conditioned walkers moved by
+// more than 1e-5 relative through this product, a fourth product lo * lo changing nothing, a centred form r - 1/2 0.25 - 0.7 %:
+// profiles/r04_parity_attribution_cpu.txt); in the real kernel it is below the fp32 roundings of everything else: DESIGN.md section 6.)
+template <int D, int NBK, int T>
 __device__ __forceinline__ void hidden_layers(const float* net, const float (&in)[T][D], int lane, Frag (&h2)[T][2], f32x16 (&pend)[T]) {
     using O = NetOff<D, NBK>;
     const int h = lane >> 5;
@@ -347,28 +240,27 @@ __device__ __forceinline__ void hidden_layers(const float* net, const float (&in
             }
         }
     }
-    act8<T, CENTER>(a[0], 0, h1, 0);
-    act8<T, CENTER>(a[0], 1, h1, 0);
+    act8<T>(a[0], 0, h1, 0);
+    act8<T>(a[0], 1, h1, 0);
     const _Float16* W1h = reinterpret_cast<const _Float16*>(net + O::W1h);
     const _Float16* W1l = reinterpret_cast<const _Float16*>(net + O::W1l);
-    constexpr int kB1 = CENTER ? O::b1c : O::b1;
     f32x16 c0[T];
     {
-        const f32x16 bias = load16(net + kB1 + h * 16);
+        const f32x16 bias = load16(net + O::b1 + h * 16);
 #pragma unroll
         for (int t = 0; t < T; ++t) c0[t] = bias;
     }
     WF_PIN();
     mfma_step<T>(W1h, W1l, 0, 0, h1, c0, lane);
-    act8<T, CENTER>(a[1], 0, h1, 1);
+    act8<T>(a[1], 0, h1, 1);
     WF_PIN();
     mfma_step<T>(W1h, W1l, 0, 1, h1, c0, lane);
-    act8<T, CENTER>(a[1], 1, h1, 1);
+    act8<T>(a[1], 1, h1, 1);
     WF_PIN();
     mfma_step<T>(W1h, W1l, 1, 0, h1, c0, lane);
     mfma_step<T>(W1h, W1l, 1, 1, h1, c0, lane);
     {
-        const f32x16 bias = load16(net + kB1 + (2 + h) * 16);
+        const f32x16 bias = load16(net + O::b1 + (2 + h) * 16);
 #pragma unroll
         for (int t = 0; t < T; ++t) pend[t] = bias;
     }
@@ -447,7 +339,7 @@ __device__ __forceinline__ void fetch_block(f32x16 (&A)[NO], f32x16 (&Bv)[NO], c
         }
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
-            const f32x4 a = load4g(reinterpret_cast<const float*>(tb + off + o * 32)), b = load4g(reinterpret_cast<const float*>(tb + offb + o * 32));
+            const f32x4 a = load4(reinterpret_cast<const float*>(tb + off + o * 32)), b = load4(reinterpret_cast<const float*>(tb + offb + o * 32));
 #pragma unroll
             for (int e = 0; e < 4; ++e) { A[o][q * 4 + e] = a[e]; Bv[o][q * 4 + e] = b[e]; }
         }
@@ -485,12 +377,12 @@ __device__ __forceinline__ void rows_lerp_dot(const f32x16 (&v)[NBK], const floa
     auto row_sums = [&]() {   // rsum: [mesh]{R0_m, R1_m, R0_{m+1}, R1_{m+1}} (NO == 2 only): one 16-byte record holds both lerp ends
         if (rsum) {
             static_assert(NO <= 2, "row sums: orders 0 and 1");
-            const f32x4 c = load4g(rsum + (size_t)Lp.il * 4);
+            const f32x4 c = load4(rsum + (size_t)Lp.il * 4);
             f32x4 r = c;
             bool far = false;
             if (FAR) {
                 far = Lp.ir != Lp.il && Lp.ir != Lp.il + 1;
-                r = load4g(rsum + (size_t)Lp.ir * 4);
+                r = load4(rsum + (size_t)Lp.ir * 4);
             }
 #pragma unroll
             for (int o = 0; o < NO; ++o) {
@@ -564,34 +456,6 @@ __device__ __forceinline__ void sigmoid_block(f32x16 (&o)[NBK], const float* fk_
     Sf = xhalf_sum(sf);
 }
 
-#if defined(WF_STAMP) && defined(WF_STAMP_TILE)
-// per-tile variant: slot (iteration & 7) accumulates the wave's elapsed cycles of that iteration of the tile loop (slot 0 includes the prologue)
-#define STAMP(k)                                                                                   \
-    do {                                                                                           \
-        if ((k) == 6) {                                                                            \
-            __builtin_amdgcn_sched_barrier(0);                                                     \
-            unsigned long long t_;                                                                 \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");             \
-            __builtin_amdgcn_sched_barrier(0);                                                     \
-            stamp_acc[stamp_iter & 7] += t_ - stamp_last;                                          \
-            stamp_last = t_;                                                                       \
-            ++stamp_iter;                                                                          \
-        }                                                                                          \
-    } while (0)
-#elif defined(WF_STAMP)
-#define STAMP(k)                                                                                   \
-    do {                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        unsigned long long t_;                                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                 \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        stamp_acc[k] += t_ - stamp_last;                                                           \
-        stamp_last = t_;                                                                           \
-    } while (0)
-#else
-#define STAMP(k)
-#endif
-
 // cooperative copy of n_floats (multiple of 4) global -> LDS, 16 B per lane
 template <int kThreads>
 __device__ __forceinline__ void stage_floats(const float* __restrict__ src, float* dst, int n_floats) {
@@ -639,7 +503,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
     // (SPEC at D = 2: every net resident, a compile-time fact of that family; SPEC at D > 2 -- the electron chains -- may run staged)
     const int prior_kind = SPEC ? (int)WF_PRIOR_WAVEFLOW : mm.prior_kind, staged = (SPEC && D == 2) ? 0 : mm.staged, exact_div = SPEC ? 0 : mm.exact_div;
     // Resident mode hands the workgroup's tiles to its waves through a counter in LDS instead of a fixed share per wave: the SIMD's issue
-    // arbitration favours its oldest wave (measured with per-tile s_memtime stamps: at 16 waves the first tile of SIMD slot 0 takes 39 k
+    // arbitration favours its oldest wave (measured with per-tile cycle-counter stamps: at 16 waves the first tile of SIMD slot 0 takes 39 k
     // cycles, that of slot 3 151 k), so with equal shares the old waves leave early and the last tiles run at one or two waves per SIMD --
     // a quarter of the launch time was that tail.  Every wave leaves the loop when the counter passes the workgroup's share.
     __shared__ int next_slot;
@@ -665,19 +529,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
     const float rn_mesh = 1.0f / (float)(mm.n_mesh - 1);
     // wave-uniform terms of the mean-type box transform's first step, held in scalar registers (the compiler hoists them into vector ones)
     const float box_space0 = uniform_f(2 * L + tol), box_nlog0 = uniform_f(0.0f - fast_log(2 * L + tol));
-#ifdef WF_STAMP
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last;
-    [[maybe_unused]] int stamp_iter = 0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
-    [[maybe_unused]] const unsigned long long stamp_t0 = stamp_last;
-#endif
-
-#ifdef WF_STAGGER
-    // The waves of one SIMD (w, w + 4, w + 8, ...) run the same program on tiles of equal cost and would stay in lockstep: matrix
-    // phases against matrix phases, table-load waits against table-load waits.  A one-off start delay of a quarter / half net period
-    // per SIMD slot keeps them out of phase (there is no barrier after this point in resident mode).
-    for (int q = 0; q < ((wave >> 2) & 3); ++q) __builtin_amdgcn_s_sleep(WF_STAGGER);
-#endif
     int f16_bad = 0;   // wave-uniform: scalar loads
     if (mm.f16_ovf)
         for (int n = 0; n < mm.n_nets; ++n) f16_bad |= mm.f16_ovf[n];
@@ -757,9 +608,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
         {
             Frag h2[T][2];
             f32x16 pend[T];
-            STAMP(0);
-            hidden_layers<D, NBK, T, kCenter>(net, cur, lane, h2, pend);
-            STAMP(1);
+            hidden_layers<D, NBK, T>(net, cur, lane, h2, pend);
             if (layer_kind == WF_LAYER_IMADE) {
                 // dimension 0: walker-independent weights -> composite table (k_prepare_dim0)
 #pragma unroll
@@ -770,12 +619,14 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
                     nxt[t][0] = c0[0];
                     logdet[t] = logdet[t] + fast_log(c0[1] + 1e-7f);
                 }
-                STAMP(2);
                 const bool gate_i = !SPEC && mm.i_gate != 0;
                 float gl[T];   // gate of dimension d: prod_{i<d} (layer input)_i^3
 #pragma unroll
                 for (int t = 0; t < T; ++t) gl[t] = 1.0f;
-#pragma unroll (kDimUnroll<D>)
+                // the loops over a net's output dimensions are unrolled.  Rolled for the long chains (D > 4; round 4): no spilled registers at 8 waves
+                // instead of 10, 75 / 207 at 12 / 16 waves instead of 172 / 346 -- and 2 - 5 % SLOWER at 8 waves (D = 8, 2^18 walkers: 0.319 against
+                // 0.314 ms), 12 and 16 waves slower still (0.365 / 0.472 ms): profiles/r04_c4_rolled_loops_and_waves.txt.  Same bits either way.
+#pragma unroll (D)
                 for (int d = 1; d < D; ++d) {
                     if (D > 4) __builtin_amdgcn_sched_barrier(0);   // long chains: one dimension at a time (the scheduler otherwise keeps the records of several dimensions in flight: 29 -> 218 spilled registers at 12 waves)
                     if (gate_i) {
@@ -791,7 +642,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
 #pragma unroll
                         for (int t = 0; t < T; ++t) v[t][kb] = o[t];
                     }
-                    STAMP(3);
                     // (Requesting the table rows before the output MFMAs, or before the sigmoids -- they depend on the layer input only --
                     // costs 64 * NBK live registers per tile: spills at 12 and 16 waves, -2 % at 8; r02 notes in DESIGN.md.)
 #pragma unroll
@@ -799,14 +649,13 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
                         float S1, Sf;
                         sigmoid_block<NBK>(v[t], fkI, h, S1, Sf, gate_i, gl[t], net + NetOff<D, NBK>::z + d * NBK * 32);
                         const float rs = mm.i_reg * S1;
-                        const float rS = x_rcp(__builtin_fmaf(rs, mm.F_I, Sf));
+                        const float rS = __builtin_amdgcn_rcpf(__builtin_fmaf(rs, mm.F_I, Sf));
                         const Lerp Lp = make_lerp(cur[t][d], mm.n_mesh, rn_mesh, exact_div);
                         if (IDX && idx[t]) { idx[t][(l * D + d) * 2] = Lp.xl; idx[t][(l * D + d) * 2 + 1] = Lp.xr; }
                         float ld;
                         ispline_eval<NBK>(v[t], mm.tabI, mm.rsI, Lp, h, bndI, rS, rs, nxt[t][d], ld);
                         logdet[t] = logdet[t] + ld;
                     }
-                    STAMP(5);
                 }
             } else {
                 // MADE (made.py:21-27): rows 0 / 1 of block d = log_weight / bias (lane half 0, registers 0 / 1)
@@ -863,7 +712,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
                 const bool gate_p = !SPEC && mm.p_gate != 0;   // gated head: prod_{i<d} u_i^3 of the conditioner's input, the unclipped u
 #pragma unroll
                 for (int t = 0; t < T; ++t) { lp[t] = 0.0f; prod[t] = 1.0f; gp[t] = 1.0f; }
-#pragma unroll (kDimUnroll<D>)
+#pragma unroll (D)
                 for (int d = 0; d < D; ++d) {
                     if (D > 4) __builtin_amdgcn_sched_barrier(0);
                     if (gate_p && d > 0) {
@@ -942,9 +791,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
                                         const _Float16* blk = obh + (size_t)(ko * NBK + ki) * 2048;
                                         const f16x8 ah = *reinterpret_cast<const f16x8*>(blk + (s * 64 + lane) * 8);
                                         const f16x8 al = *reinterpret_cast<const f16x8*>(blk + 1024 + (s * 64 + lane) * 8);
-#ifdef WF_MFMA_4PROD
-                                        c[ko] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, of[ki].lo[s], c[ko], 0, 0, 0);
-#endif
                                         c[ko] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, of[ki].hi[s], c[ko], 0, 0, 0);
                                         c[ko] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, of[ki].lo[s], c[ko], 0, 0, 0);
                                         c[ko] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, of[ki].hi[s], c[ko], 0, 0, 0);
@@ -958,7 +804,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
 #pragma unroll
                                 for (int r = 0; r < 16; ++r) n2 = __builtin_fmaf(c[ko][r], c[ko][r], n2);
                             }
-                            const float rnorm = x_rsq(xhalf_sum(n2));
+                            const float rnorm = __builtin_amdgcn_rsqf(xhalf_sum(n2));
                             const float v0 = rows_dot<NBK>(c, mm.tabP, Lp[t], h, bndP) * rnorm;
                             val[t] = (s1 < 0.0f && !mm.prior_quotient) ? -v0 : v0;
                         }
@@ -1062,7 +908,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
             load_box(w, valid, cur, logdet);
             for (int l = 0; l < mm.n_layers; ++l) flow_layer(l, slots + (size_t)l * mm.net_floats, cur, logdet, idx);
             head_store(slots + (size_t)mm.n_layers * mm.net_floats, cur, logdet, w, valid, idx);
-            STAMP(6);
         }
     } else {
         // Staged mode (the nets do not fit LDS together): ONE slot.  A super-chunk = kWaves * T * tps tiles; every wave walks its tps
@@ -1112,18 +957,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
             }
         }
     }
-#ifdef WF_STAMP
-    if (mm.dbg && lane == 0) {
-        unsigned long long* g = reinterpret_cast<unsigned long long*>(mm.dbg) + ((size_t)blockIdx.x * kWaves + wave) * 8;
-#ifdef WF_STAMP_SPAN   // absolute start / finish of the wave's tile loop and its number of iterations; [3]: finish on the 100 MHz
-        // constant clock (s_memrealtime), which unlike s_memtime is comparable between workgroups on different XCDs
-        g[0] = stamp_t0; g[1] = stamp_last; g[2] = (unsigned long long)stamp_iter;
-        { unsigned long long rt_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_)::"memory"); g[3] = rt_; }
-#else
-        for (int k = 0; k < 8; ++k) g[k] = stamp_acc[k];
-#endif
-    }
-#endif
 }
 
 template <int D, int NBK, int kWaves, int T, bool IDX, bool SPEC>

@@ -153,7 +153,7 @@ static inline int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h;
 
 static int mfma_net_floats(int D, int nbk) {
     const int S0 = (D + 1) / 2;
-    return 128 * S0 + 64 + 4096 + 64 + (D - 1) * nbk * 2048 + 32 * D * nbk + 32 * D * nbk + 64;   // ..., biases, zero_params, unfolded b1 (NetOff::b1c)
+    return 128 * S0 + 64 + 4096 + 64 + (D - 1) * nbk * 2048 + 32 * D * nbk + 32 * D * nbk + 64;   // ..., biases, zero_params, reserved tail (NetOff::reserved)
 }
 
 // per-row factor: remove_bias scaling (isplines_jax.py:196-202 / msplines_jax.py:186-192) times the
@@ -305,8 +305,8 @@ static void describe_mfma_image(const wf_model* m, int n, uint32_t base, std::ve
                     if (sig) w.f32_abs(src);
                     else w.f32(src);
                 }
-    // NetOff::b1c: the second hidden layer's bias as c1 * b1, which k_fold_bias leaves alone -- for the centred first-layer activations
-    // (r - 1/2) of k_mfma's flow nets (wf_mfma_impl.h: hidden_layers<..., CENTER>)
+    // NetOff::reserved: the image's last 64 floats, which no kernel reads.  They keep what was always written there (the second hidden layer's
+    // bias as c1 * b1, which k_fold_bias leaves alone), so that the image stays byte for byte what it was.
     for (int ob = 0; ob < 2; ++ob)
         for (int h = 0; h < 2; ++h)
             for (int r = 0; r < 16; ++r) w.f32(q.b1 + 32 * ob + acc_row(r, h), c1);
