@@ -238,6 +238,15 @@ int wf_sample(const wf_model* m, uint64_t seed, int64_t B, float* x_dev, float* 
 int wf_hamiltonian_fwd(const wf_model* m, const float* x_dev, int64_t B, const float* protons_host, int32_t n_protons,
                        float* hpsi_dev, float* psi_dev, float* laplacian_dev, void* stream);
 
+/* Coordinate derivatives of psi per walker: grad_dev[B][D] = d psi / d x_d -- jax.grad(psi, argnums=1) of the reference's closure -- and
+ * hdiag_dev[B][D] = d^2 psi / d x_d^2, the diagonal of the jax.hessian that physics.laplacian traces (utils/physics.py:50-52): what the drift
+ * grad / (psi + 1e-8) (the regulariser of vqmc.py:196), per-electron kinetic energies and gradient-form kinetic estimators are made of.  Same
+ * derivative rule as wf_hamiltonian_fwd (the table lerp differentiates to the next cached table, isplines_jax.py:60-66), so the sum of
+ * hdiag over d is its Laplacian.  psi_dev[B] and hdiag_dev may be NULL; grad_dev is required (NULL with B > 0: WF_ERR_INVALID).  Sorted
+ * walkers, the domain, the model coverage, the refusals and the three kernel paths of wf_hamiltonian_fwd (same switch points and knobs; with
+ * hdiag_dev the two-particle matrix-core kernels carry the two second derivatives apart). */
+int wf_psi_coord_derivs(const wf_model* m, const float* x_dev, int64_t B, float* psi_dev, float* grad_dev, float* hdiag_dev, void* stream);
+
 /* Parameter gradient of psi and of its Laplacian -- the vector-Jacobian product behind vqmc.train_step_efficient
  * (vqmc.py:193-221: value_and_grad of loss_fn_efficient through physics.laplacian, utils/physics.py:50-52):
  *     grad_dev[p] = sum_b ( w_psi_dev[b] * d psi_b / d theta_p + w_lap_dev[b] * d laplacian(psi)_b / d theta_p )

@@ -79,7 +79,7 @@ EXPORTS = ["wf_abi_version", "wf_strerror", "wf_last_hip_error", "wf_last_hip_er
            "wf_vqmc_train_step", "wf_vqmc_train_step_workspace_bytes", "wf_nsc_fwd", "wf_nsc_workspace_bytes", "wf_logpdf_loss_grad", "wf_mle_train_step", "wf_mle_train_step_workspace_bytes", "wf_vqmc_train_step_local",
            "wf_vqmc_train_step_apply", "wf_psi_antisym_fwd", "wf_logpdf_unsorted_fwd", "wf_inversion_count",
            "wf_spline_create", "wf_spline_destroy", "wf_spline_n_bases", "wf_spline_apply", "wf_spline_reverse", "wf_spline_enforce_bc",
-           "wf_spline_remove_bias", "wf_spline_sample"]
+           "wf_spline_remove_bias", "wf_spline_sample", "wf_psi_coord_derivs"]
 
 _lib = None
 
@@ -139,6 +139,8 @@ def lib():
     L.wf_sample.argtypes = [vp, ctypes.c_uint64, i64, vp, vp, i32, vp]
     L.wf_hamiltonian_fwd.restype = i32
     L.wf_hamiltonian_fwd.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp]
+    L.wf_psi_coord_derivs.restype = i32
+    L.wf_psi_coord_derivs.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.wf_psi_vjp_workspace_bytes.restype = i64
     L.wf_psi_vjp_workspace_bytes.argtypes = [vp, i64]
     L.wf_psi_vjp.restype = i32

@@ -245,6 +245,23 @@ class DeviceModel:
             res.append(back(lap))
         return res[0] if len(res) == 1 else tuple(res)
 
+    def psi_derivatives(self, x, hessian_diag=False, return_psi=False):
+        """d psi / d x_d -> [B, D] (jax.grad(psi, 1)); with hessian_diag also d^2 psi / d x_d^2 -> [B, D] (the diagonal of jax.hessian(psi, 1),
+        whose row sums are the Laplacian of `hamiltonian`).  Returns grad, or (grad[, hdiag][, psi]); sorted walkers, numpy or torch like `hamiltonian`."""
+        t, back = self._to_dev(x)
+        B = t.shape[0]
+        grad = self._new((B, self.D))
+        hd = self._new((B, self.D)) if hessian_diag else None
+        ps = self._new((B,)) if return_psi else None
+        _lib.check(_lib.lib().wf_psi_coord_derivs(self._h, self._p(t), B, self._p(ps), self._p(grad), self._p(hd), self._stream()),
+                   "wf_psi_coord_derivs")
+        res = [back(grad)]
+        if hessian_diag:
+            res.append(back(hd))
+        if return_psi:
+            res.append(back(ps))
+        return res[0] if len(res) == 1 else tuple(res)
+
     def psi_vjp(self, x, w_psi, w_lap):
         """grad[p] = sum_b (w_psi[b] d psi_b/d theta_p + w_lap[b] d laplacian_b/d theta_p) -> torch.cuda float32 [n_params]."""
         torch = _torch()

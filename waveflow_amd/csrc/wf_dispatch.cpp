@@ -284,6 +284,51 @@ int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* 
 
 using namespace wf;
 
+// What wf_hamiltonian_fwd and wf_psi_coord_derivs refuse beyond check_fwd, in this order
+static int check_energy_model(const wf_model* m) {
+    if (m->desc.prior_kind != WF_PRIOR_WAVEFLOW) return WF_ERR_INVALID;
+    if (!m->wave_ok || !m->d_tabP3 || !m->d_grad_fk) return WF_ERR_UNSUPPORTED;
+    if (m->desc.n_flow_layers > 0 && m->desc.layer_kind != WF_LAYER_IMADE) return WF_ERR_UNSUPPORTED;
+    return WF_OK;
+}
+
+// The three paths of the local energy, shared by every entry point that runs its kernels: one set of predicates, switch points and chunk sizes.
+// tile / dir / wave(c0, bc, ws) launch walkers [c0, c0 + bc) with the exchange buffer ws (tile: null = the one-launch form, the whole batch);
+// tile_floats(bc): the exchange buffer of the launch-per-net form of the two-particle tile path.
+template <class Tile, class Dir, class Wave>
+static int run_energy_paths(const wf_model* m, int64_t B, int64_t (*tile_floats)(int64_t), Tile&& tile, Dir&& dir, Wave&& wave) {
+    const int D = m->desc.n_dim;
+    // one launch per chunk of the batch
+    auto in_chunks = [&](int64_t chunk, int64_t floats, auto&& launch) -> int {
+        int rc = ensure_scratch(m, floats);
+        if (rc) return rc;
+        for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+            rc = launch(c0, std::min(chunk, B - c0), m->d_scratch);
+            if (rc) return rc;
+        }
+        return WF_OK;
+    };
+    // Large batches of the two-particle family: conditioner jets on the matrix cores + lane-per-walker heads (wf_kernels_etile.hip).
+    // WF_ENERGY_TILE_MIN (read per call) moves the switch point; 0 disables the path.
+    if (energy_tile2_capable_at(m, B) && tiles_fresh(m)) {
+        if (energy_tile_fused(&m->mdev))   // every net resident in LDS: one launch for the whole batch, no exchange buffer (k_efused)
+            return tile(0, B, nullptr);
+        // the conditioner and the head kernels exchange 384 B per walker and net through the scratch buffer: chunks that keep it
+        // (and its re-use by the next net and the next chunk) inside the 256 MB memory-side cache instead of HBM
+        const int64_t tchunk = std::min<int64_t>(B, std::max<int64_t>(env_energy_tile_chunk(), 1024));
+        return in_chunks(tchunk, tile_floats(tchunk), tile);
+    }
+    // Large batches beyond two particles: one coordinate direction at a time with Taylor triples on the matrix cores (wf_kernels_etile_dir.hip), the same
+    // switch point and knobs as the two-particle tile path
+    if (energy_dir_capable_at(m, B) && tiles_fresh(m)) {
+        const int64_t dchunk = std::min<int64_t>(B, (int64_t)1 << 18);   // 12 D (D + 1) bytes of jets per walker: 226 MB at D = 8
+        return in_chunks(dchunk, energy_dir_floats(dchunk, D), dir);
+    }
+    // the wave sweeps (wf_kernels_wave.hip): every batch size, every model these entry points accept
+    const int64_t chunk = std::min<int64_t>(B, (int64_t)1 << 20);
+    return in_chunks(chunk, chunk * wave_tail_floats(D, 1), wave);
+}
+
 extern "C" {
 
 int wf_logpdf_fwd(const wf_model* m, const float* x_dev, int64_t B, float* logp_dev, float* u_dev, int32_t* bin_idx_dev,
@@ -393,51 +438,51 @@ int wf_hamiltonian_fwd(const wf_model* m, const float* x_dev, int64_t B, const f
     if (rc) return rc;
     Protons pr{};
     if (!make_protons(protons_host, n_protons, &pr)) return WF_ERR_INVALID;
-    if (m->desc.prior_kind != WF_PRIOR_WAVEFLOW) return WF_ERR_INVALID;
-    if (!m->wave_ok || !m->d_tabP3 || !m->d_grad_fk) return WF_ERR_UNSUPPORTED;
-    if (m->desc.n_flow_layers > 0 && m->desc.layer_kind != WF_LAYER_IMADE) return WF_ERR_UNSUPPORTED;
+    rc = check_energy_model(m);
+    if (rc) return rc;
     DeviceGuard g(m->device);
     if (B == 0) return WF_OK;
     const int D = m->desc.n_dim;
-    // one launch per chunk of the batch (psi and the Laplacian are optional outputs)
-    auto in_chunks = [&](int64_t chunk, auto&& launch) -> int {
-        for (int64_t c0 = 0; c0 < B; c0 += chunk) {
-            int rcl = launch(x_dev + c0 * D, std::min(chunk, B - c0), hpsi_dev + c0, psi_dev ? psi_dev + c0 : nullptr, laplacian_dev ? laplacian_dev + c0 : nullptr);
-            if (rcl) return rcl;
-        }
-        return WF_OK;
-    };
-    // Large batches of the two-particle family: conditioner jets on the matrix cores + lane-per-walker heads (wf_kernels_etile.hip).
-    // WF_ENERGY_TILE_MIN (read per call) moves the switch point; 0 disables the path.
-    if (energy_tile2_capable_at(m, B) && tiles_fresh(m)) {
-        if (energy_tile_fused(&m->mdev))   // every net resident in LDS: one launch for the whole batch, no exchange buffer (k_efused)
-            return launch_energy_tile(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, m->d_grad_fk, x_dev, B, pr, hpsi_dev, psi_dev, laplacian_dev, nullptr, stream);
-        // the conditioner and the head kernels exchange 384 B per walker and net through the scratch buffer: chunks that keep it
-        // (and its re-use by the next net and the next chunk) inside the 256 MB memory-side cache instead of HBM
-        const int64_t tchunk = std::min<int64_t>(B, std::max<int64_t>(env_energy_tile_chunk(), 1024));
-        rc = ensure_scratch(m, energy_tile_floats(tchunk));
-        if (rc) return rc;
-        return in_chunks(tchunk, [&](const float* x, int64_t bc, float* hpsi, float* psi, float* lap) {
-            return launch_energy_tile(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, m->d_grad_fk, x, bc, pr, hpsi, psi, lap, m->d_scratch, stream);
+    // psi and the Laplacian are optional outputs
+    auto psi = [&](int64_t c0) { return psi_dev ? psi_dev + c0 : nullptr; };
+    auto lap = [&](int64_t c0) { return laplacian_dev ? laplacian_dev + c0 : nullptr; };
+    return run_energy_paths(
+        m, B, energy_tile_floats,
+        [&](int64_t c0, int64_t bc, float* ws) {
+            return launch_energy_tile(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, m->d_grad_fk, x_dev + c0 * D, bc, pr, hpsi_dev + c0, psi(c0), lap(c0), ws, stream);
+        },
+        [&](int64_t c0, int64_t bc, float* ws) {
+            return launch_energy_dir(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, x_dev + c0 * D, bc, pr, hpsi_dev + c0, psi(c0), lap(c0), ws, stream);
+        },
+        [&](int64_t c0, int64_t bc, float* ws) {
+            return launch_wave_energy(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x_dev + c0 * D, bc, pr, hpsi_dev + c0, psi(c0), lap(c0), ws, stream);
         });
-    }
-    // Large batches beyond two particles: one coordinate direction at a time with Taylor triples on the matrix cores (wf_kernels_etile_dir.hip), the same
-    // switch point and knobs as the two-particle tile path
-    if (energy_dir_capable_at(m, B) && tiles_fresh(m)) {
-        const int64_t dchunk = std::min<int64_t>(B, (int64_t)1 << 18);   // 12 D (D + 1) bytes of jets per walker: 226 MB at D = 8
-        rc = ensure_scratch(m, energy_dir_floats(dchunk, D));
-        if (rc) return rc;
-        return in_chunks(dchunk, [&](const float* x, int64_t bc, float* hpsi, float* psi, float* lap) {
-            return launch_energy_dir(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, x, bc, pr, hpsi, psi, lap, m->d_scratch, stream);
-        });
-    }
-    // the wave sweeps (wf_kernels_wave.hip): every batch size, every model this entry point accepts
-    const int64_t chunk = std::min<int64_t>(B, (int64_t)1 << 20);
-    rc = ensure_scratch(m, chunk * wave_tail_floats(D, 1));
+}
+
+int wf_psi_coord_derivs(const wf_model* m, const float* x_dev, int64_t B, float* psi_dev, float* grad_dev, float* hdiag_dev, void* stream) {
+    int rc = check_fwd(m, x_dev, B, grad_dev);
     if (rc) return rc;
-    return in_chunks(chunk, [&](const float* x, int64_t bc, float* hpsi, float* psi, float* lap) {
-        return launch_wave_energy(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x, bc, pr, hpsi, psi, lap, m->d_scratch, stream);
-    });
+    rc = check_energy_model(m);
+    if (rc) return rc;
+    DeviceGuard g(m->device);
+    if (B == 0) return WF_OK;
+    const int D = m->desc.n_dim;
+    auto psi = [&](int64_t c0) { return psi_dev ? psi_dev + c0 : nullptr; };
+    auto hd = [&](int64_t c0) { return hdiag_dev ? hdiag_dev + c0 * D : nullptr; };
+    return run_energy_paths(
+        m, B, derivs_tile_floats,
+        // two particles: k_efused (gradient: J's a and b; with the Hessian diagonal: the five-component jet), or launch by launch
+        [&](int64_t c0, int64_t bc, float* ws) {
+            return launch_derivs_tile(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, m->d_grad_fk, x_dev + c0 * D, bc, psi(c0), grad_dev + c0 * D, hd(c0), ws, stream);
+        },
+        // beyond two particles: k_edir's prior launch writes every direction's first and second derivative
+        [&](int64_t c0, int64_t bc, float* ws) {
+            return launch_derivs_dir(&m->mdev, m->dev, m->d_tabI4c, m->d_tabP4c, x_dev + c0 * D, bc, psi(c0), grad_dev + c0 * D, hd(c0), ws, stream);
+        },
+        // the directional wave sweep (R3) and one lane per walker behind it
+        [&](int64_t c0, int64_t bc, float* ws) {
+            return launch_wave_derivs(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x_dev + c0 * D, bc, psi(c0), grad_dev + c0 * D, hd(c0), ws, stream);
+        });
 }
 
 int64_t wf_psi_vjp_workspace_bytes(const wf_model* m, int64_t B) { return vjp_ws_bytes(m, B, true); }

@@ -42,6 +42,35 @@ __device__ __forceinline__ J jr(J x) {
 // table function of a jet argument: value t0, first / second derivative t1 / t2 (the lerps of the next two cached orders)
 __device__ __forceinline__ J jlift(float t0, float t1, float t2, J u) { return japply(u, t0, t1, t2); }
 
+// The two-particle jet with the second derivatives kept apart (wf_psi_coord_derivs with the Hessian diagonal): value, d/dx0, d/dx1,
+// (d^2/dx0^2) / 2, (d^2/dx1^2) / 2 -- J's h is the sum of the last two.  Same per-walker algebra, one component more.
+struct J5 {
+    float v, a, b, h, k;
+};
+__device__ __forceinline__ J5 operator+(J5 x, J5 y) { return J5{x.v + y.v, x.a + y.a, x.b + y.b, x.h + y.h, x.k + y.k}; }
+__device__ __forceinline__ J5 operator-(J5 x, J5 y) { return J5{x.v - y.v, x.a - y.a, x.b - y.b, x.h - y.h, x.k - y.k}; }
+__device__ __forceinline__ J5 operator+(J5 x, float c) { return J5{x.v + c, x.a, x.b, x.h, x.k}; }
+__device__ __forceinline__ J5 operator*(J5 x, float c) { return J5{x.v * c, x.a * c, x.b * c, x.h * c, x.k * c}; }
+__device__ __forceinline__ J5 operator*(J5 x, J5 y) {
+    return J5{x.v * y.v, x.v * y.a + y.v * x.a, x.v * y.b + y.v * x.b, x.v * y.h + y.v * x.h + x.a * y.a, x.v * y.k + y.v * x.k + x.b * y.b};
+}
+__device__ __forceinline__ J5 japply(J5 x, float f, float f1, float f2) {
+    return J5{f, f1 * x.a, f1 * x.b, f1 * x.h + 0.5f * f2 * (x.a * x.a), f1 * x.k + 0.5f * f2 * (x.b * x.b)};
+}
+__device__ __forceinline__ J5 jrcp(J5 x) { const float f = 1.0f / x.v; return japply(x, f, -f * f, 2.0f * f * f * f); }
+__device__ __forceinline__ J5 jlog(J5 x) { const float f1 = 1.0f / x.v; return japply(x, logf(x.v), f1, -f1 * f1); }
+__device__ __forceinline__ J5 jexp_half(J5 x) { const float f = expf(0.5f * x.v); return japply(x, f, 0.5f * f, 0.25f * f); }
+__device__ __forceinline__ J5 jlift(float t0, float t1, float t2, J5 u) { return japply(u, t0, t1, t2); }
+// constants and the coordinates x0, x1 in either jet
+template <class JT> __device__ __forceinline__ JT jcst(float c);
+template <> __device__ __forceinline__ J jcst<J>(float c) { return J{c, 0.0f, 0.0f, 0.0f}; }
+template <> __device__ __forceinline__ J5 jcst<J5>(float c) { return J5{c, 0.0f, 0.0f, 0.0f, 0.0f}; }
+template <class JT> __device__ __forceinline__ JT jvar(float x, int d) {
+    JT r = jcst<JT>(x);
+    (d == 0 ? r.a : r.b) = 1.0f;
+    return r;
+}
+
 // ---- Two-variable Taylor algebra for the heads.  Behind the conditioner everything a head sums over its rows is SEPARABLE in the layer's two
 // inputs: the weights v_j are functions of s = u_0 alone (the conditioner's Taylor triple), the table rows T_j functions of t = u_1 alone.
 // So the row loop accumulates plain scalars -- sum_j v_j^(a)(s) g_j T_j^(k)(t) for the few (a, k) the second-order expansion needs -- and
@@ -68,6 +97,11 @@ __device__ __forceinline__ J t2jet(T2 F, J s, J t) {
     return J{F.f, F.s * s.a + F.t * t.a, F.s * s.b + F.t * t.b,
              F.s * s.h + F.t * t.h + 0.5f * (F.ss * (s.a * s.a + s.b * s.b) + 2.0f * F.st * (s.a * t.a + s.b * t.b) + F.tt * (t.a * t.a + t.b * t.b))};
 }
+__device__ __forceinline__ J5 t2jet(T2 F, J5 s, J5 t) {
+    return J5{F.f, F.s * s.a + F.t * t.a, F.s * s.b + F.t * t.b,
+              F.s * s.h + F.t * t.h + 0.5f * (F.ss * (s.a * s.a) + 2.0f * F.st * (s.a * t.a) + F.tt * (t.a * t.a)),
+              F.s * s.k + F.t * t.k + 0.5f * (F.ss * (s.b * s.b) + 2.0f * F.st * (s.b * t.b) + F.tt * (t.b * t.b))};
+}
 // r(x) = 1 / (2^x + 1) of a pre-activation triple (x, x', x'') in s -> (r, r', r'')
 __device__ __forceinline__ void r_triple(float x0, float x1, float x2, float& v0, float& v1, float& v2) {
     const float r = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x0) + 1.0f);
@@ -86,6 +120,18 @@ __device__ __forceinline__ J st_load(const float* __restrict__ st, int slot, int
 __device__ __forceinline__ void st_store(float* __restrict__ st, int slot, int64_t B, int64_t w, J x) {
     float* p = st + (int64_t)slot * 4 * B + w;
     p[0] = x.v; p[B] = x.a; p[2 * B] = x.b; p[3 * B] = x.h;
+}
+// J5: the first four components where J's are (k_etile_cond reads the values there), the fifth of slot s behind the three slots: st[(12 + s) * B + w]
+template <class JT> __device__ __forceinline__ JT st_get(const float* __restrict__ st, int slot, int64_t B, int64_t w);
+template <> __device__ __forceinline__ J st_get<J>(const float* __restrict__ st, int slot, int64_t B, int64_t w) { return st_load(st, slot, B, w); }
+template <> __device__ __forceinline__ J5 st_get<J5>(const float* __restrict__ st, int slot, int64_t B, int64_t w) {
+    const float* p = st + (int64_t)slot * 4 * B + w;
+    return J5{p[0], p[B], p[2 * B], p[3 * B], st[(int64_t)(12 + slot) * B + w]};
+}
+__device__ __forceinline__ void st_store(float* __restrict__ st, int slot, int64_t B, int64_t w, J5 x) {
+    float* p = st + (int64_t)slot * 4 * B + w;
+    p[0] = x.v; p[B] = x.a; p[2 * B] = x.b; p[3 * B] = x.h;
+    st[(int64_t)(12 + slot) * B + w] = x.k;
 }
 
 
@@ -167,8 +213,9 @@ __device__ __forceinline__ LerpN nlerp(float x, int n_mesh) {
 
 // y_1 = N_0 / Q and log(dy_1 + 1e-7) from the row sums of one flow head (see T2): N_k(s, t) = V_k(s, t) / S(s) + reg R_k(t), k = 0 (value) and 1
 // (derivative in t), Q(s) = Qv(s) / S(s) + reg G
+template <class JT>
 __device__ __forceinline__ void flow_head_finish(const float (&S)[3], const float (&Qv)[3], const float (&R)[4], float G, const float (&V0)[4],
-                                                 const float (&V1)[3], const float (&V2)[2], float reg, J u0, J u1, J& y1, J& ld) {
+                                                 const float (&V1)[3], const float (&V2)[2], float reg, JT u0, JT u1, JT& y1, JT& ld) {
     const T2 iS = t2rcp(T2{S[0], S[1], 0.0f, S[2], 0.0f, 0.0f});
     const T2 Q = T2{Qv[0], Qv[1], 0.0f, Qv[2], 0.0f, 0.0f} * iS + reg * G;
     const T2 rQ = t2rcp(Q);

@@ -163,6 +163,9 @@ bool energy_dir_capable(const MfmaDev* mdev);
 int64_t energy_dir_floats(int64_t B, int D);
 int launch_energy_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, const Protons& pr,
                       float* hpsi, float* psi, float* lap, float* ws, void* stream);
+// ... and the coordinate derivatives of psi from the same launches (wf_psi_coord_derivs): psi and hdiag may be null
+int launch_derivs_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, float* psi, float* grad,
+                      float* hdiag, float* ws, void* stream);
 // parameter gradients of psi and its Laplacian on the matrix cores (two-particle family, <= 64 bases; k_efused in wf_kernels_etile.hip, k_ebwd per net and k_egrad_reduce in wf_kernels_etile_bwd.hip)
 bool energy_vjp_capable(const MfmaDev* mdev);
 int64_t energy_vjp_floats_per_walker(int n_nets);
@@ -174,6 +177,10 @@ int launch_energy_vjp(const MfmaDev* mdev, const ModelDev& md, const float* tabI
 int launch_energy_vjp_finish(const float* gacc, int n_nets, int nbk, const int* offs, const float* c2, float* flat, int64_t n_params, void* stream);   // the one-kernel form applies (nets resident in LDS; WF_ENERGY_FUSED=0 switches it off per call)
 int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x, int64_t B,
                        const Protons& pr, float* hpsi, float* psi, float* lap, float* ws, void* stream, float* st_out = nullptr);
+// ... and the coordinate derivatives of psi (wf_psi_coord_derivs): psi and hdiag may be null; ws (launch-per-net form): derivs_tile_floats(B)
+int64_t derivs_tile_floats(int64_t B);
+int launch_derivs_tile(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x, int64_t B,
+                       float* psi, float* grad, float* hdiag, float* ws, void* stream);
 // The sweeps run over a coefficient ring (wf_ring.h).  kind 0: R1 (first order); 1: R3 (one sample per walker and direction,
 // 3 coefficients); 2: RF<K> (one sample per walker and block of K directions, K + 2 coefficients); 3: RF<D> (one sample per walker).
 // The taped sweeps use kind 2 with K = D up to 5 coordinates; beyond, the 8..10 live floats per value of RF<D> spill hundreds of registers
@@ -201,6 +208,8 @@ int launch_zgrad_reduce(const float* zws, int64_t n_samples, int n_rows, int acc
 int launch_zgrad_scatter(const float* zgrad, int n_rows, const int32_t* zmap, const int32_t* zraw_off, const float* plain, float* grad_flat, void* stream);
 int launch_wave_energy(const ModelDev& md, const ModelDev* md_dev, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x,
                        int64_t B, const Protons& pr, float* hpsi, float* psi, float* lap, float* tail_ws, void* stream);
+int launch_wave_derivs(const ModelDev& md, const ModelDev* md_dev, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x,
+                       int64_t B, float* psi, float* grad, float* hdiag, float* tail_ws, void* stream);
 // staged inverse / sampler of large two-particle batches (wf_kernels_etile_sample.hip: conditioners on the matrix cores, one lane per walker elsewhere)
 bool tile_sample_capable(const MfmaDev* mdev);
 int64_t tile_sample_floats(int64_t B, int nbk);

@@ -24,6 +24,8 @@
 // (the gradient path: wf_etile_bwd.h, wf_kernels_etile_bwd.hip; the staged inverse / sampler: wf_kernels_etile_sample.hip)
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "wf_etile_cond.h"
 
 // The jet / Taylor algebra of this file is checked against oracles by tolerance, not by operation order: multiply-add pairs may fuse (the build's
@@ -36,20 +38,22 @@ namespace wf {
 namespace {
 // ---------------------------------------------------------------------------- lane-per-walker stages
 // BoxTransformLayer, mean type, two particles (made.py:156-183) as jets of (x0, x1)
+// (JT = J: H psi; J5: the coordinate derivatives with the Hessian diagonal -- here and in the two head kernels below)
+template <class JT = J>
 __global__ void k_etile_box(const float* __restrict__ xg, int64_t B, float L, float* __restrict__ st) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const float tol = 1e-7f;
-    const J x0 = J{xg[b * 2], 1.0f, 0.0f, 0.0f}, x1 = J{xg[b * 2 + 1], 0.0f, 1.0f, 0.0f};
-    const J mean = (x0 + x1) * 0.5f;
-    const J l = mean - x0, wd = x1 - x0;
-    J ld = jc(0.0f);
-    const J space = jc(2 * L);
-    const J diff = x1 - x0;
-    const J u0 = diff * jrcp(space + tol);
+    const JT x0 = jvar<JT>(xg[b * 2], 0), x1 = jvar<JT>(xg[b * 2 + 1], 1);
+    const JT mean = (x0 + x1) * 0.5f;
+    const JT l = mean - x0, wd = x1 - x0;
+    JT ld = jcst<JT>(0.0f);
+    const JT space = jcst<JT>(2 * L);
+    const JT diff = x1 - x0;
+    const JT u0 = diff * jrcp(space + tol);
     ld = ld - jlog(space + tol);
-    const J den = (jc(2 * L) - wd) + tol;
-    const J u1 = ((mean + L) - l) * jrcp(den);
+    const JT den = (jcst<JT>(2 * L) - wd) + tol;
+    const JT u1 = ((mean + L) - l) * jrcp(den);
     ld = ld - jlog(den);
     st_store(st, 0, B, b, u0);
     st_store(st, 1, B, b, u1);
@@ -57,15 +61,16 @@ __global__ void k_etile_box(const float* __restrict__ xg, int64_t B, float L, fl
 }
 
 // One IMADE layer behind its conditioner (made.py:66-81) + Reverse: dimension 0 from the composite table, dimension 1 from the head jets
+template <class JT = J>
 __global__ __launch_bounds__(256) void k_etile_flow(const float4_t* __restrict__ comp /* this net: [n_mesh] {Y, Y', Y'', Y'''} */,
                                                     const float* __restrict__ tabI /* [n_mesh][8 row chunks][4 orders][4 rows] */, const float* __restrict__ gI, int nb,
                                                     int n_mesh, float reg, const float* __restrict__ oj, int64_t B, float* __restrict__ st) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const J u0 = st_load(st, 0, B, b), u1 = st_load(st, 1, B, b);
-    J ld = st_load(st, 2, B, b);
+    const JT u0 = st_get<JT>(st, 0, B, b), u1 = st_get<JT>(st, 1, B, b);
+    JT ld = st_get<JT>(st, 2, B, b);
     // ---- dimension 0
-    J y0;
+    JT y0;
     {
         const LerpN L = nlerp(u0.v, n_mesh);
         const float4_t ca = comp[L.il], cb = comp[L.ir];
@@ -121,26 +126,29 @@ __global__ __launch_bounds__(256) void k_etile_flow(const float4_t* __restrict__
             G += g;
         }
     }
-    J y1;
+    JT y1;
     flow_head_finish(S, Qv, R, G, V0, V1, V2, reg, u0, u1, y1, ld);
     st_store(st, 0, B, b, y1);   // Reverse (bijections.py:337-340)
     st_store(st, 1, B, b, y0);
     st_store(st, 2, B, b, ld);
 }
 
-// Waveflow prior (wavefunctions.py:54-71) + H psi (physics.py:60-93)
+// Waveflow prior (wavefunctions.py:54-71) + H psi (physics.py:60-93); DERIV (wf_psi_coord_derivs): psi (may be null), its gradient and -- JT = J5 -- the
+// diagonal of its Hessian instead
+template <class JT = J, bool DERIV = false>
 __global__ __launch_bounds__(256) void k_etile_prior(const float4_t* __restrict__ comp /* prior: {P, P', P''} with sign and norm */,
                                                      const float* __restrict__ tabP /* orthogonal B, [n_mesh][8][4][4] like tabI */, int nb, int n_mesh,
                                                      unsigned constrained_mask, const float* __restrict__ oj, const float* __restrict__ s1buf,
                                                      const float* __restrict__ st, const float* __restrict__ xg, int64_t B, const Protons pr,
-                                                     float* __restrict__ hpsi, float* __restrict__ psi_out, float* __restrict__ lap_out) {
+                                                     float* __restrict__ hpsi, float* __restrict__ psi_out, float* __restrict__ lap_out,
+                                                     float* __restrict__ grad_out = nullptr, float* __restrict__ hdiag_out = nullptr) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const J u0 = st_load(st, 0, B, b), u1 = st_load(st, 1, B, b), ld = st_load(st, 2, B, b);
+    const JT u0 = st_get<JT>(st, 0, B, b), u1 = st_get<JT>(st, 1, B, b), ld = st_get<JT>(st, 2, B, b);
     // the spline sees the clipped coordinate (:45): outside [0, 1] it is a constant
-    const J uc0 = (u0.v < 0.0f) ? jc(0.0f) : (u0.v > 1.0f ? jc(1.0f) : u0);
-    const J uc1 = (u1.v < 0.0f) ? jc(0.0f) : (u1.v > 1.0f ? jc(1.0f) : u1);
-    J val0;
+    const JT uc0 = (u0.v < 0.0f) ? jcst<JT>(0.0f) : (u0.v > 1.0f ? jcst<JT>(1.0f) : u0);
+    const JT uc1 = (u1.v < 0.0f) ? jcst<JT>(0.0f) : (u1.v > 1.0f ? jcst<JT>(1.0f) : u1);
+    JT val0;
     {
         const LerpN L = nlerp(uc0.v, n_mesh);
         const float4_t ca = comp[L.il], cb = comp[L.ir];
@@ -183,24 +191,34 @@ __global__ __launch_bounds__(256) void k_etile_prior(const float4_t* __restrict_
     const float sgn = s1buf[b] < 0.0f ? -1.0f : 1.0f;
     const T2 N2 = T2{cc, 2.0f * cc1, 0.0f, 2.0f * (c1c1 + cc2), 0.0f, 0.0f};
     const T2 dotp = T2{D0[0], D1[0], D0[1], D2, D1[1], D0[2]};
-    const J val1 = t2jet(dotp * t2rsqrt(N2), u0, uc1) * sgn;
+    const JT val1 = t2jet(dotp * t2rsqrt(N2), u0, uc1) * sgn;
     const float sc0 = (constrained_mask & 1u) ? 0.70710678118654752f : 1.0f, sc1 = (constrained_mask & 2u) ? 0.70710678118654752f : 1.0f;
-    const J psi = ((val0 * sc0) * (val1 * sc1)) * jexp_half(ld);
-    const float lap = 2.0f * psi.h;
-    float V = 0.0f;   // physics.py:60-76
-    for (int p = 0; p < pr.n; ++p)
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const float r = pr.pos[p] - xg[b * 2 + d];
-            V -= 1.0f / sqrtf(1.0f + r * r);
+    const JT psi = ((val0 * sc0) * (val1 * sc1)) * jexp_half(ld);
+    if constexpr (DERIV) {
+        if (psi_out) psi_out[b] = psi.v;
+        grad_out[b * 2] = psi.a;
+        grad_out[b * 2 + 1] = psi.b;
+        if constexpr (std::is_same<JT, J5>::value) {
+            hdiag_out[b * 2] = 2.0f * psi.h;
+            hdiag_out[b * 2 + 1] = 2.0f * psi.k;
         }
-    {
-        const float r = xg[b * 2 + 1] - xg[b * 2];
-        V += 1.0f / sqrtf(1.0f + r * r);
+    } else {
+        const float lap = 2.0f * psi.h;
+        float V = 0.0f;   // physics.py:60-76
+        for (int p = 0; p < pr.n; ++p)
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                const float r = pr.pos[p] - xg[b * 2 + d];
+                V -= 1.0f / sqrtf(1.0f + r * r);
+            }
+        {
+            const float r = xg[b * 2 + 1] - xg[b * 2];
+            V += 1.0f / sqrtf(1.0f + r * r);
+        }
+        hpsi[b] = -0.5f * lap + V * psi.v;
+        if (psi_out) psi_out[b] = psi.v;
+        if (lap_out) lap_out[b] = lap;
     }
-    hpsi[b] = -0.5f * lap + V * psi.v;
-    if (psi_out) psi_out[b] = psi.v;
-    if (lap_out) lap_out[b] = lap;
 }
 
 // ---------------------------------------------------------------------------- H psi in ONE kernel (every net resident in LDS)
@@ -212,25 +230,30 @@ __global__ __launch_bounds__(256) void k_etile_prior(const float4_t* __restrict_
 // (round 4, 2^20 walkers, one / two row blocks: 8 waves 0.81 / 1.16 ms, 6 waves 0.88 / 1.36, 4 waves -- no spills -- 0.98 / 1.31, 12 waves -- 133 / 330 spilled -- 0.96 / 2.21, 16 waves 2.31 / 3.98)
 constexpr int kFusedWaves = 8;
 
-__device__ __forceinline__ void box_mean2(float x0v, float x1v, float L, J& u0, J& u1, J& ld) {   // (k_etile_box)
+template <class JT>
+__device__ __forceinline__ void box_mean2(float x0v, float x1v, float L, JT& u0, JT& u1, JT& ld) {   // (k_etile_box)
     const float tol = 1e-7f;
-    const J x0 = J{x0v, 1.0f, 0.0f, 0.0f}, x1 = J{x1v, 0.0f, 1.0f, 0.0f};
-    const J mean = (x0 + x1) * 0.5f;
-    const J l = mean - x0, wd = x1 - x0;
-    const J space = jc(2 * L);
-    const J diff = x1 - x0;
+    const JT x0 = jvar<JT>(x0v, 0), x1 = jvar<JT>(x1v, 1);
+    const JT mean = (x0 + x1) * 0.5f;
+    const JT l = mean - x0, wd = x1 - x0;
+    const JT space = jcst<JT>(2 * L);
+    const JT diff = x1 - x0;
     u0 = diff * jrcp(space + tol);
-    ld = jc(0.0f) - jlog(space + tol);
-    const J den = (jc(2 * L) - wd) + tol;
+    ld = jcst<JT>(0.0f) - jlog(space + tol);
+    const JT den = (jcst<JT>(2 * L) - wd) + tol;
     u1 = ((mean + L) - l) * jrcp(den);
     ld = ld - jlog(den);
 }
 // PBIAS: the B prior's boundary map has a constant term (a constraint with a non-zero value): its own instantiation, so that the derivative channels'
 // sums do not lengthen live ranges in the common one
-template <int NBK, bool PBIAS = false>
+// OUT (wf_psi_coord_derivs): 0: H psi;  1: psi (may be null) and its gradient, J's a and b;  2: ... and the diagonal of its Hessian -- the per-walker jet
+// is J5 (the conditioner's three MFMA channels and the separable row sums are those of OUT = 0: only the per-walker algebra behind them grows)
+template <int NBK, bool PBIAS = false, int OUT = 0>
 __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, const float* __restrict__ tabI, const float* __restrict__ tabP,
                                                              const float* __restrict__ xg, int64_t B, const Protons pr, float* __restrict__ hpsi,
-                                                             float* __restrict__ psi_out, float* __restrict__ lap_out, float* __restrict__ st_out) {
+                                                             float* __restrict__ psi_out, float* __restrict__ lap_out, float* __restrict__ st_out,
+                                                             float* __restrict__ grad_out = nullptr /* OUT >= 1: [B][2] */, float* __restrict__ hdiag_out = nullptr /* OUT = 2: [B][2] */) {
+    using JT = typename std::conditional<OUT == 2, J5, J>::type;
     // st_out (may be null): the (u_0, u_1, log det) jets at the input of every net, [net][slot][channel][B] -- what the gradient path's
     // per-net reverse kernels (k_ebwd) restart from
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -266,12 +289,12 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
         const bool valid = w < B;
         const int64_t wl = valid ? w : B - 1;
         const float x0v = xg[wl * 2], x1v = xg[wl * 2 + 1];
-        J u0, u1, ld;
+        JT u0, u1, ld;
         box_mean2(x0v, x1v, mm.box_L, u0, u1, ld);
         // ---- flow layers (made.py:66-81 + Reverse)
         for (int l = 0; l < mm.n_layers; ++l) {
             const float* net = lds + mm.const_floats + (size_t)l * mm.net_floats;
-            if (st_out && valid && h == 0) {
+            if (OUT == 0 && st_out && valid && h == 0) {
                 st_store(st_out + (size_t)l * 12 * B, 0, B, w, u0);
                 st_store(st_out + (size_t)l * 12 * B, 1, B, w, u1);
                 st_store(st_out + (size_t)l * 12 * B, 2, B, w, ld);
@@ -280,7 +303,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
             int e[NCH];
             cond_hidden<NBK>(net, u0.v, u1.v, lane, f, e);
             // dimension 0: composite table of the net, all four orders
-            J y0;
+            JT y0;
             {
                 const LerpN L0 = nlerp(u0.v, n_mesh);
                 const float4_t* comp = mm.comp + (size_t)l * n_mesh;
@@ -305,16 +328,16 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
             for (int k = 0; k < 4; ++k) { a.R[k] = xhalf_sum(a.R[k]); a.V0[k] = xhalf_sum(a.V0[k]); }
 #pragma unroll
             for (int k = 0; k < 2; ++k) a.V2[k] = xhalf_sum(a.V2[k]);
-            J y1;
+            JT y1;
             flow_head_finish(a.S, a.Qv, a.R, mm.F_I, a.V0, a.V1, a.V2, mm.i_reg, u0, u1, y1, ld);
             u0 = y1;   // Reverse (bijections.py:337-340)
             u1 = y0;
         }
         // ---- Waveflow prior (wavefunctions.py:54-71)
-        J psi;
+        JT psi;
         {
             const float* net = lds + mm.const_floats + (size_t)mm.n_layers * mm.net_floats;
-            if (st_out && valid && h == 0) {
+            if (OUT == 0 && st_out && valid && h == 0) {
                 st_store(st_out + (size_t)mm.n_layers * 12 * B, 0, B, w, u0);
                 st_store(st_out + (size_t)mm.n_layers * 12 * B, 1, B, w, u1);
                 st_store(st_out + (size_t)mm.n_layers * 12 * B, 2, B, w, ld);
@@ -331,9 +354,9 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
                 for (int kb = 0; kb < NBK; ++kb) cond_out<NBK>(net, f, e, kb, lane, o[kb]);
                 prior_frags<NBK>(o, fkP, lane, of, eo, s1, PBIAS ? sder : nullptr);
             }
-            const J uc0 = (u0.v < 0.0f) ? jc(0.0f) : (u0.v > 1.0f ? jc(1.0f) : u0);   // the spline sees the clipped coordinate (:45)
-            const J uc1 = (u1.v < 0.0f) ? jc(0.0f) : (u1.v > 1.0f ? jc(1.0f) : u1);
-            J val0;
+            const JT uc0 = (u0.v < 0.0f) ? jcst<JT>(0.0f) : (u0.v > 1.0f ? jcst<JT>(1.0f) : u0);   // the spline sees the clipped coordinate (:45)
+            const JT uc1 = (u1.v < 0.0f) ? jcst<JT>(0.0f) : (u1.v > 1.0f ? jcst<JT>(1.0f) : u1);
+            JT val0;
             {
                 const LerpN L0 = nlerp(uc0.v, n_mesh);
                 const float4_t* comp = mm.comp + (size_t)mm.n_layers * n_mesh;
@@ -364,11 +387,22 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_efused(const MfmaDev mm, c
             const float sgn = s1 < 0.0f ? -1.0f : 1.0f;
             const T2 N2 = T2{a.cc, 2.0f * a.cc1, 0.0f, 2.0f * (a.c1c1 + a.cc2), 0.0f, 0.0f};
             const T2 dotp = T2{a.D0[0], a.D1[0], a.D0[1], a.D2, a.D1[1], a.D0[2]};
-            const J val1 = t2jet(dotp * t2rsqrt(N2), u0, uc1) * sgn;
+            const JT val1 = t2jet(dotp * t2rsqrt(N2), u0, uc1) * sgn;
             const float sc0 = (mm.constrained_mask & 1u) ? 0.70710678118654752f : 1.0f, sc1 = (mm.constrained_mask & 2u) ? 0.70710678118654752f : 1.0f;
             psi = ((val0 * sc0) * (val1 * sc1)) * jexp_half(ld);
         }
-        if (valid && h == 0) {
+        if constexpr (OUT != 0) {
+            if (valid && h == 0) {   // (a packed weight outside the fp16 range: NaN, as below)
+                const float nan = __builtin_nanf("");
+                if (psi_out) psi_out[w] = f16_bad ? nan : psi.v;
+                grad_out[w * 2] = f16_bad ? nan : psi.a;
+                grad_out[w * 2 + 1] = f16_bad ? nan : psi.b;
+                if constexpr (OUT == 2) {
+                    hdiag_out[w * 2] = f16_bad ? nan : 2.0f * psi.h;
+                    hdiag_out[w * 2 + 1] = f16_bad ? nan : 2.0f * psi.k;
+                }
+            }
+        } else if (valid && h == 0) {
             const float lap = 2.0f * psi.h;
             float V = 0.0f;   // physics.py:60-76
             for (int p = 0; p < pr.n; ++p) {
@@ -398,12 +432,15 @@ bool energy_tile_fused(const MfmaDev* mdev) {
 
 // workspace: state (12 floats), head triples (96 floats), the sign sum (1 float) per walker
 int64_t energy_tile_floats(int64_t B) { return B * (12 + 1) + ((B + 31) / 32) * 32 * (32 * NCH); }   // state, s1, head triples of whole tiles
+int64_t derivs_tile_floats(int64_t B) { return energy_tile_floats(B) + 3 * B; }                        // ... and the fifth component of the three state jets
 
 // mdev: the model's MFMA description (resident or not: one net is staged per launch); md: ModelDev on the host (spline sizes, masks)
-int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x, int64_t B,
-                       const Protons& pr, float* hpsi, float* psi, float* lap, float* ws, void* stream, float* st_out) {
+// grad == null: H psi (hpsi, psi, lap; st_out);  else the coordinate derivatives of psi (psi, grad, hdiag: either may be null but grad)
+static int launch_tile(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x, int64_t B,
+                       const Protons& pr, float* hpsi, float* psi, float* lap, float* ws, void* stream, float* st_out, float* grad, float* hdiag) {
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) return WF_OK;
+    const int out = !grad ? 0 : (hdiag ? 2 : 1);
     // every net resident in LDS (the shipped shapes): the whole of H psi in one launch, nothing through HBM but the walkers and the results.
     // WF_ENERGY_FUSED=0 (read per call) keeps the launch-per-net path below (A/B tests; models whose nets do not fit together take it anyway).
     {
@@ -411,11 +448,16 @@ int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tab
             const int lds_all = (mdev->const_floats + mdev->net_floats * mdev->n_nets) * (int)sizeof(float);
             const int64_t n_tiles = (B + 31) / 32;
             const unsigned blocks = (unsigned)std::min<int64_t>((n_tiles + kFusedWaves - 1) / kFusedWaves, 256);
-#define WF_EFUSED(NBK_, PB_)                                                                                                                   \
+#define WF_EFUSED_OUT(NBK_, PB_, OUT_)                                                                                                         \
     {                                                                                                                                          \
         static DynLdsSlots cfg{};                                                                                                              \
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_efused<NBK_, PB_>), lds_all, &cfg)) return rc;                          \
-        hipLaunchKernelGGL((k_efused<NBK_, PB_>), dim3(blocks), dim3(kFusedWaves * 64), lds_all, s, *mdev, tabI4, tabP4, x, B, pr, hpsi, psi, lap, st_out); \
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_efused<NBK_, PB_, OUT_>), lds_all, &cfg)) return rc;                    \
+        hipLaunchKernelGGL((k_efused<NBK_, PB_, OUT_>), dim3(blocks), dim3(kFusedWaves * 64), lds_all, s, *mdev, tabI4, tabP4, x, B, pr, hpsi, psi, lap, st_out, \
+                           grad, hdiag);                                                                                                       \
+    }
+#define WF_EFUSED(NBK_, PB_)                                                                                                                   \
+    {                                                                                                                                          \
+        if (out == 0) WF_EFUSED_OUT(NBK_, PB_, 0) else if (out == 1) WF_EFUSED_OUT(NBK_, PB_, 1) else WF_EFUSED_OUT(NBK_, PB_, 2)                \
     }
             if (mdev->nbk == 1) {
                 if (mdev->p_bias) WF_EFUSED(1, true) else WF_EFUSED(1, false)
@@ -423,11 +465,12 @@ int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tab
                 if (mdev->p_bias) WF_EFUSED(2, true) else WF_EFUSED(2, false)
             }
 #undef WF_EFUSED
+#undef WF_EFUSED_OUT
             return check();
         }
     }
-    float* st = ws;
-    float* s1 = st + 12 * B;
+    float* st = ws;   // [12 B] state jets, J5: + [3 B] their fifth components
+    float* s1 = st + (out == 2 ? 15 : 12) * B;
     float* oj = s1 + B;
     const unsigned lane_blocks = (unsigned)((B + 255) / 256);
     const int lds_bytes = (mdev->const_floats + mdev->net_floats) * (int)sizeof(float);
@@ -436,16 +479,35 @@ int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tab
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_etile_cond<true>), lds_bytes, &cfg_prior)) return rc;
     const int64_t n_tiles = (B + 31) / 32;
     const unsigned cond_blocks = (unsigned)std::min<int64_t>((n_tiles + kCondWaves - 1) / kCondWaves, 256 * 4);
-    hipLaunchKernelGGL(k_etile_box, dim3(lane_blocks), dim3(256), 0, s, x, B, md.box_L, st);
+    if (out == 2) hipLaunchKernelGGL(k_etile_box<J5>, dim3(lane_blocks), dim3(256), 0, s, x, B, md.box_L, st);
+    else hipLaunchKernelGGL(k_etile_box<J>, dim3(lane_blocks), dim3(256), 0, s, x, B, md.box_L, st);
     for (int l = 0; l < md.n_layers; ++l) {
         hipLaunchKernelGGL(k_etile_cond<false>, dim3(cond_blocks), dim3(kCondWaves * 64), lds_bytes, s, *mdev, l, (const float*)st, B, oj, s1);
-        hipLaunchKernelGGL(k_etile_flow, dim3(lane_blocks), dim3(256), 0, s, mdev->comp + (size_t)l * mdev->n_mesh, tabI4, fk_nat, md.isp.nb,
-                           md.isp.n_mesh, md.i_reg, (const float*)oj, B, st);
+        if (out == 2)
+            hipLaunchKernelGGL(k_etile_flow<J5>, dim3(lane_blocks), dim3(256), 0, s, mdev->comp + (size_t)l * mdev->n_mesh, tabI4, fk_nat, md.isp.nb,
+                               md.isp.n_mesh, md.i_reg, (const float*)oj, B, st);
+        else
+            hipLaunchKernelGGL(k_etile_flow<J>, dim3(lane_blocks), dim3(256), 0, s, mdev->comp + (size_t)l * mdev->n_mesh, tabI4, fk_nat, md.isp.nb,
+                               md.isp.n_mesh, md.i_reg, (const float*)oj, B, st);
     }
     hipLaunchKernelGGL(k_etile_cond<true>, dim3(cond_blocks), dim3(kCondWaves * 64), lds_bytes, s, *mdev, md.n_layers, (const float*)st, B, oj, s1);
-    hipLaunchKernelGGL(k_etile_prior, dim3(lane_blocks), dim3(256), 0, s, mdev->comp + (size_t)md.n_layers * mdev->n_mesh, tabP4, md.psp.nb,
-                       md.psp.n_mesh, md.constrained_mask, (const float*)oj, (const float*)s1, (const float*)st, x, B, pr, hpsi, psi, lap);
+#define WF_EPRIOR(JT_, DERIV_)                                                                                                                        \
+    hipLaunchKernelGGL((k_etile_prior<JT_, DERIV_>), dim3(lane_blocks), dim3(256), 0, s, mdev->comp + (size_t)md.n_layers * mdev->n_mesh, tabP4, md.psp.nb, \
+                       md.psp.n_mesh, md.constrained_mask, (const float*)oj, (const float*)s1, (const float*)st, x, B, pr, hpsi, psi, lap, grad, hdiag)
+    if (out == 2) WF_EPRIOR(J5, true);
+    else if (out == 1) WF_EPRIOR(J, true);
+    else WF_EPRIOR(J, false);
+#undef WF_EPRIOR
     return check();
+}
+int launch_energy_tile(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x, int64_t B,
+                       const Protons& pr, float* hpsi, float* psi, float* lap, float* ws, void* stream, float* st_out) {
+    return launch_tile(mdev, md, tabI4, tabP4, fk_nat, x, B, pr, hpsi, psi, lap, ws, stream, st_out, nullptr, nullptr);
+}
+int launch_derivs_tile(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x, int64_t B,
+                       float* psi, float* grad, float* hdiag, float* ws, void* stream) {
+    if (!grad) return WF_ERR_INVALID;
+    return launch_tile(mdev, md, tabI4, tabP4, fk_nat, x, B, Protons{}, nullptr, psi, nullptr, ws, stream, nullptr, grad, hdiag);
 }
 
 }  // namespace wf

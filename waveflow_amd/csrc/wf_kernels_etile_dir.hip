@@ -127,10 +127,13 @@ __device__ __forceinline__ J comp_jet(const float4_t* __restrict__ comp, const J
 // One net of the model for every (tile, direction).  Flow nets (PRIOR = false): IMADE layer + Reverse (made.py:66-81, bijections.py:337-340), the
 // jets go back to st.  Prior (PRIOR = true): Waveflow prior (wavefunctions.py:54-71) for every direction of the tile, Laplacian = sum of the second
 // derivatives, H psi (physics.py:60-93).
-template <int D, bool PRIOR>
+// DERIV (PRIOR only; wf_psi_coord_derivs): every direction's d psi / d x_dir and d^2 psi / d x_dir^2 go out instead of their sum and H psi.
+template <int D, bool PRIOR, bool DERIV = false>
 __global__ __launch_bounds__(kDirWaves * 64) void k_edir(const MfmaDev mm, int net_index, const float* __restrict__ tabI, const float* __restrict__ tabP,
                                                          float* __restrict__ st, int64_t B, const float* __restrict__ xg, const Protons pr,
-                                                         float* __restrict__ hpsi, float* __restrict__ psi_out, float* __restrict__ lap_out) {
+                                                         float* __restrict__ hpsi, float* __restrict__ psi_out, float* __restrict__ lap_out,
+                                                         float* __restrict__ grad_out = nullptr /* DERIV: [B][D] */, float* __restrict__ hdiag_out = nullptr /* DERIV: [B][D], may be null */) {
+    static_assert(PRIOR || !DERIV, "the derivatives leave from the prior's launch");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int next_item;
     __shared__ int bnd_s[32];   // support bounds of the table chunks: [I: 8][lo, hi], [prior: 8][lo, hi]
@@ -238,8 +241,16 @@ __global__ __launch_bounds__(kDirWaves * 64) void k_edir(const MfmaDev mm, int n
                 }
                 lap += 2.0f * psi.h;
                 psiv = psi.v;
+                if constexpr (DERIV) {
+                    if (valid && h == 0) {
+                        grad_out[w * D + dir] = psi.a;
+                        if (hdiag_out) hdiag_out[w * D + dir] = 2.0f * psi.h;
+                    }
+                }
             }
-            if (valid && h == 0) {
+            if constexpr (DERIV) {
+                if (valid && h == 0 && psi_out) psi_out[w] = psiv;
+            } else if (valid && h == 0) {
                 float V = 0.0f;   // physics.py:60-76: soft-Coulomb, one space dimension
                 for (int p = 0; p < pr.n; ++p)
 #pragma unroll
@@ -262,20 +273,26 @@ __global__ __launch_bounds__(kDirWaves * 64) void k_edir(const MfmaDev mm, int n
     }
 }
 
+// grad == null: H psi (hpsi, psi, lap);  else the coordinate derivatives (psi, grad, hdiag)
 template <int D>
 int launch_dir_t(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, const Protons& pr, float* hpsi,
-                 float* psi, float* lap, float* st, hipStream_t s) {
+                 float* psi, float* lap, float* grad, float* hdiag, float* st, hipStream_t s) {
     const int lds_bytes = (mdev->const_floats + mdev->net_floats) * (int)sizeof(float);
-    static DynLdsSlots cfg_f{}, cfg_p{};
+    static DynLdsSlots cfg_f{}, cfg_p{}, cfg_d{};
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_edir<D, false>), lds_bytes, &cfg_f)) return rc;
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_edir<D, true>), lds_bytes, &cfg_p)) return rc;
+    if (grad) {
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_edir<D, true, true>), lds_bytes, &cfg_d)) return rc;
+    } else if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_edir<D, true>), lds_bytes, &cfg_p)) return rc;
     const int64_t n_tiles = (B + 31) / 32;
     hipLaunchKernelGGL(k_edir_box<D>, dim3((unsigned)((B + 255) / 256), D), dim3(256), 0, s, x, B, md.box_L, st);
     const unsigned gf = (unsigned)std::min<int64_t>((n_tiles * D + kDirWaves - 1) / kDirWaves, 256);
     const unsigned gp = (unsigned)std::min<int64_t>((n_tiles + kDirWaves - 1) / kDirWaves, 256);
     for (int l = 0; l < md.n_layers; ++l)
-        hipLaunchKernelGGL((k_edir<D, false>), dim3(gf), dim3(kDirWaves * 64), lds_bytes, s, *mdev, l, tabI4, tabP4, st, B, x, pr, hpsi, psi, lap);
-    hipLaunchKernelGGL((k_edir<D, true>), dim3(gp), dim3(kDirWaves * 64), lds_bytes, s, *mdev, md.n_layers, tabI4, tabP4, st, B, x, pr, hpsi, psi, lap);
+        hipLaunchKernelGGL((k_edir<D, false>), dim3(gf), dim3(kDirWaves * 64), lds_bytes, s, *mdev, l, tabI4, tabP4, st, B, x, pr, hpsi, psi, lap, (float*)nullptr, (float*)nullptr);
+    if (grad)
+        hipLaunchKernelGGL((k_edir<D, true, true>), dim3(gp), dim3(kDirWaves * 64), lds_bytes, s, *mdev, md.n_layers, tabI4, tabP4, st, B, x, pr, hpsi, psi, lap, grad, hdiag);
+    else
+        hipLaunchKernelGGL((k_edir<D, true>), dim3(gp), dim3(kDirWaves * 64), lds_bytes, s, *mdev, md.n_layers, tabI4, tabP4, st, B, x, pr, hpsi, psi, lap, grad, hdiag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_hip_error((int)e);
@@ -291,19 +308,29 @@ bool energy_dir_capable(const MfmaDev* mdev) {
     return mdev->D >= 3 && mdev->D <= 8 && mdev->nbk == 1 && mdev->n_layers >= 0 && mdev->n_layers < kMaxLayers && !mdev->i_gate && !mdev->p_gate && !mdev->p_bias &&
            mdev->comp != nullptr && (mdev->const_floats + mdev->net_floats) * 4 <= 160 * 1024 - 512;
 }
-int launch_energy_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, const Protons& pr,
-                      float* hpsi, float* psi, float* lap, float* ws, void* stream) {
+static int launch_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, const Protons& pr,
+                      float* hpsi, float* psi, float* lap, float* grad, float* hdiag, float* ws, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) return WF_OK;
     switch (md.D) {
-        case 3: return launch_dir_t<3>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, ws, s);
-        case 4: return launch_dir_t<4>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, ws, s);
-        case 5: return launch_dir_t<5>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, ws, s);
-        case 6: return launch_dir_t<6>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, ws, s);
-        case 7: return launch_dir_t<7>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, ws, s);
-        case 8: return launch_dir_t<8>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, ws, s);
+        case 3: return launch_dir_t<3>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, grad, hdiag, ws, s);
+        case 4: return launch_dir_t<4>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, grad, hdiag, ws, s);
+        case 5: return launch_dir_t<5>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, grad, hdiag, ws, s);
+        case 6: return launch_dir_t<6>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, grad, hdiag, ws, s);
+        case 7: return launch_dir_t<7>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, grad, hdiag, ws, s);
+        case 8: return launch_dir_t<8>(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, grad, hdiag, ws, s);
     }
     return WF_ERR_UNSUPPORTED;
+}
+int launch_energy_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, const Protons& pr,
+                      float* hpsi, float* psi, float* lap, float* ws, void* stream) {
+    return launch_dir(mdev, md, tabI4, tabP4, x, B, pr, hpsi, psi, lap, nullptr, nullptr, ws, stream);
+}
+// the same box and flow launches; the prior's launch writes psi.a and 2 psi.h of every direction (no potential, no H psi)
+int launch_derivs_dir(const MfmaDev* mdev, const ModelDev& md, const float* tabI4, const float* tabP4, const float* x, int64_t B, float* psi, float* grad,
+                      float* hdiag, float* ws, void* stream) {
+    if (!grad) return WF_ERR_INVALID;
+    return launch_dir(mdev, md, tabI4, tabP4, x, B, Protons{}, nullptr, psi, nullptr, grad, hdiag, ws, stream);
 }
 
 }  // namespace wf

@@ -566,6 +566,25 @@ __global__ void k_energy_out(const float* __restrict__ tails, const float* __res
     if (lap_out) lap_out[b] = lap;
 }
 
+// ---- the coordinate derivatives of psi per walker from the R3 tails of its D directions: direction dir carries (psi, d psi / d x_dir,
+// (d^2 psi / d x_dir^2) / 2) -- jax.grad(psi, 1) and the diagonal of jax.hessian(psi, 1), what k_energy_out sums into the Laplacian
+template <int D>
+__global__ void k_derivs_out(const float* __restrict__ tails, int64_t B, unsigned constrained_mask, float* __restrict__ psi_out, float* __restrict__ grad_out,
+                             float* __restrict__ hdiag_out) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float psv = 0.0f;
+#pragma unroll
+    for (int dir = 0; dir < D; ++dir) {
+        R3 v[D], E;
+        const R3 ps = psi_from_tail<D, R3>(tails + (b * D + dir) * (int64_t)Tail<D>::N * R3::NC, constrained_mask, v, E);
+        grad_out[b * D + dir] = ps.c1;
+        if (hdiag_out) hdiag_out[b * D + dir] = lap_of(ps);
+        psv = ps.c0;
+    }
+    if (psi_out) psi_out[b] = psv;
+}
+
 // ---- log_pdf / psi / (u, log det) per walker from the R1 tails (wavefunctions.py:33-71, distributions.py:95-102, 139-163)
 // mode 0: log_pdf, 1: psi, 2: log det only;  u_out (may be null): the latent point (clipped where the reference clips it)
 template <int D>
@@ -1463,6 +1482,29 @@ int launch_wave_energy(const ModelDev& md, const ModelDev* md_dev, const float* 
     int rc = launch_wave_fwd(md, md_dev, kind, tabI4, tabP4, fk_nat, x, B, nullptr, tail_ws, 0, stream);
     if (rc) return rc;
     return launch_energy_out(md.D, kind, tail_ws, x, B, md.constrained_mask, pr, hpsi, psi, lap, stream);
+}
+
+// psi (may be null), its gradient and (may be null) the diagonal of its Hessian in the walker's coordinates: the directional R3 sweep (D samples
+// per walker, tail_ws: wave_tail_floats(D, 1) per walker), then one lane per walker
+int launch_wave_derivs(const ModelDev& md, const ModelDev* md_dev, const float* tabI4, const float* tabP4, const float* fk_nat, const float* x,
+                       int64_t B, float* psi, float* grad, float* hdiag, float* tail_ws, void* stream) {
+    int rc = launch_wave_fwd(md, md_dev, 1, tabI4, tabP4, fk_nat, x, B, nullptr, tail_ws, 0, stream);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((B + 255) / 256)), block(256);
+#define CALL(DD) hipLaunchKernelGGL(k_derivs_out<DD>, grid, block, 0, s, (const float*)tail_ws, B, md.constrained_mask, psi, grad, hdiag); break
+    switch (md.D) {
+        case 2: CALL(2);
+        case 3: CALL(3);
+        case 4: CALL(4);
+        case 5: CALL(5);
+        case 6: CALL(6);
+        case 7: CALL(7);
+        case 8: CALL(8);
+        default: return WF_ERR_UNSUPPORTED;
+    }
+#undef CALL
+    return finish();
 }
 
 }  // namespace wf

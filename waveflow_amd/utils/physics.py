@@ -37,3 +37,41 @@ def construct_hamiltonian_function(fn, protons=np.array([[0, 0]]), n_space_dimen
     h_fn.model = model
     h_fn.protons = pos
     return h_fn
+
+
+def _bound_model(fn):
+    model = getattr(fn, "model", None)
+    if model is None:
+        raise TypeError("fn must be the psi closure returned by waveflow_amd.wavefunctions.Waveflow")
+    return model
+
+
+def construct_gradient_function(fn):
+    """jax.grad(psi, argnums=1) per walker: grad_fn(params, x) -> [B, D], d psi / d x_d at sorted walkers.
+
+    The drift (quantum force) with the reference's regulariser (vqmc.py:196):
+
+        grad_fn = construct_gradient_function(psi)
+        drift = grad_fn(params, x) / (psi(params, x)[:, None] + 1e-8)
+    """
+    model = _bound_model(fn)
+
+    def grad_fn(params, x):
+        model.ensure_params(params)
+        return model.psi_derivatives(x)
+
+    grad_fn.model = model
+    return grad_fn
+
+
+def construct_hessian_diagonal_function(fn):
+    """The diagonal of jax.hessian(psi, argnums=1) per walker: hdiag_fn(params, x) -> [B, D], d^2 psi / d x_d^2; its row sums are
+    physics.laplacian (physics.py:50-52), -0.5 * hdiag / psi the per-electron kinetic energies."""
+    model = _bound_model(fn)
+
+    def hdiag_fn(params, x):
+        model.ensure_params(params)
+        return model.psi_derivatives(x, hessian_diag=True)[1]
+
+    hdiag_fn.model = model
+    return hdiag_fn
