@@ -330,6 +330,24 @@ int64_t wf_logpdf_vjp_workspace_bytes(const wf_model* m, int64_t B);
 int wf_logpdf_vjp(const wf_model* m, const float* x_dev, int64_t B, const float* w_dev, float* grad_dev, void* workspace_dev,
                   int64_t workspace_bytes, void* stream);
 
+/* Per-walker parameter Jacobians -- the un-summed object vqmc.train_step forms with jax.jacrev(log_pdf, argnums=0)(params, batch)
+ * before it contracts it (vqmc.py:179): one row of n_params entries per walker, in the flat leaf order of wf_model_set_params.
+ *     wf_logpdf_jac:  jac_dev[b][p] = d log_pdf_b / d theta_p;  logp_dev[B] (may be NULL) = log_pdf of the same forward sweep
+ *     wf_psi_jac:     jac_dev[b][p] = w_psi_dev[b] * d psi_b / d theta_p + w_lap_dev[b] * d laplacian(psi)_b / d theta_p
+ *                     (w = (1, 0): jacrev(psi); w = (0, 1): the Jacobian of the Laplacian; w_lap_dev == NULL: zeros)
+ * The sum of the rows over b is what wf_logpdf_vjp (w = 1) / wf_psi_vjp return, up to the order of the fp32 additions.  Masked-out weights and
+ * the zero_params leaves of ungated models are 0 in every row; every entry of jac_dev is written.  Model coverage and refusals are those of
+ * wf_logpdf_vjp / wf_psi_vjp.  Both always run the reverse wave sweeps and the coefficient ring the model was built with (the matrix-core
+ * gradient path keeps no tape: WF_GRAD_TILE_MIN is not consulted); k_wjac (wf_kernels_grad.hip) then forms activation x adjoint per walker.
+ * workspace: the tape only -- wf_*_jac_workspace_bytes(m, B) bytes suffice for any B, a smaller one is processed in chunks of walkers (at
+ * least one walker must fit).  A row depends on its walker alone: bitwise the same whatever the batch and the chunking. */
+int64_t wf_logpdf_jac_workspace_bytes(const wf_model* m, int64_t B);
+int wf_logpdf_jac(const wf_model* m, const float* x_dev, int64_t B, float* jac_dev, float* logp_dev, void* workspace_dev, int64_t workspace_bytes,
+                  void* stream);
+int64_t wf_psi_jac_workspace_bytes(const wf_model* m, int64_t B);
+int wf_psi_jac(const wf_model* m, const float* x_dev, int64_t B, const float* w_psi_dev, const float* w_lap_dev, float* jac_dev,
+               void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 /* Maximum-likelihood value and gradient in one pass (benchmark_tests.loss + grad(loss), benchmark_tests.py:84-101): one forward
  * sweep gives logp_dev[B] = log_pdf of every row and the tape, the reverse sweep gives grad_dev = weight * sum_b d log_pdf_b / d theta
  * (weight = -1 / N for the mean negative log-likelihood).  Workspace: wf_logpdf_vjp_workspace_bytes. */

@@ -79,7 +79,8 @@ EXPORTS = ["wf_abi_version", "wf_strerror", "wf_last_hip_error", "wf_last_hip_er
            "wf_vqmc_train_step", "wf_vqmc_train_step_workspace_bytes", "wf_nsc_fwd", "wf_nsc_workspace_bytes", "wf_logpdf_loss_grad", "wf_mle_train_step", "wf_mle_train_step_workspace_bytes", "wf_vqmc_train_step_local",
            "wf_vqmc_train_step_apply", "wf_psi_antisym_fwd", "wf_logpdf_unsorted_fwd", "wf_inversion_count",
            "wf_spline_create", "wf_spline_destroy", "wf_spline_n_bases", "wf_spline_apply", "wf_spline_reverse", "wf_spline_enforce_bc",
-           "wf_spline_remove_bias", "wf_spline_sample", "wf_psi_coord_derivs"]
+           "wf_spline_remove_bias", "wf_spline_sample", "wf_psi_coord_derivs",
+           "wf_logpdf_jac", "wf_logpdf_jac_workspace_bytes", "wf_psi_jac", "wf_psi_jac_workspace_bytes"]
 
 _lib = None
 
@@ -149,6 +150,14 @@ def lib():
     L.wf_logpdf_vjp_workspace_bytes.argtypes = [vp, i64]
     L.wf_logpdf_vjp.restype = i32
     L.wf_logpdf_vjp.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
+    for name in ("wf_logpdf_jac_workspace_bytes", "wf_psi_jac_workspace_bytes"):
+        f = getattr(L, name)
+        f.restype = i64
+        f.argtypes = [vp, i64]
+    L.wf_logpdf_jac.restype = i32
+    L.wf_logpdf_jac.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
+    L.wf_psi_jac.restype = i32
+    L.wf_psi_jac.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.wf_model_set_params_device.restype = i32
     L.wf_model_set_params_device.argtypes = [vp, vp, i64, vp]
     L.wf_adam_step.restype = i32

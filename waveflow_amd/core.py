@@ -49,6 +49,44 @@ def flatten_params(tree):
     return np.ascontiguousarray(np.concatenate(parts))
 
 
+def unflatten_batched(template, jac):
+    """[B, n_params] (numpy or torch, leaf order) -> the pytree of `template` with a leading batch axis on every leaf: what
+    jax.jacrev(f, argnums=0)(params, batch) returns for a per-walker f (vqmc.py:179).  Leaves are views of `jac`."""
+    if isinstance(template, DeviceParams):
+        template = template.template
+    if jac.ndim != 2:
+        raise ValueError(f"expected a [B, n_params] array, got shape {tuple(jac.shape)}")
+    B, n = int(jac.shape[0]), int(jac.shape[1])
+    pos = [0]
+
+    def rec(t):
+        if isinstance(t, tuple):
+            return tuple(rec(q) for q in t)
+        if isinstance(t, list):
+            return [rec(q) for q in t]
+        if t is None:
+            return None
+        shape = tuple(np.shape(t))
+        size = int(np.prod(shape, dtype=np.int64))
+        out = jac[:, pos[0]:pos[0] + size].reshape((B,) + shape)
+        pos[0] += size
+        return out
+
+    tree = rec(template)
+    if pos[0] != n:
+        raise ValueError(f"rows have {n} values, template needs {pos[0]}")
+    return tree
+
+
+def check_jacobian_bytes(B, n_params, free_bytes):
+    """A [B, n_params] float32 Jacobian must fit the free device memory: the library never spills it to the host behind the caller's back."""
+    need = int(B) * int(n_params) * 4
+    if need > int(free_bytes):
+        raise ValueError(f"a [{int(B)}, {int(n_params)}] float32 Jacobian needs {need} bytes, {int(free_bytes)} bytes of device memory are free: "
+                         "pass the walkers in smaller batches")
+    return need
+
+
 def _torch():
     import torch
     return torch
@@ -296,6 +334,48 @@ class DeviceModel:
         _lib.check(L.wf_logpdf_vjp(self._h, self._p(t), B, self._p(wt), self._p(grad), self._p(self._vjp_ws), self._vjp_ws.numel(),
                                    self._stream()), "wf_logpdf_vjp")
         return grad
+
+    def _jac_rows(self, x):
+        """-> (x on the device, empty [B, n_params] float32 cuda); ValueError if the rows do not fit the free device memory."""
+        torch = _torch()
+        shape = tuple(np.shape(x))
+        if len(shape) == 2:   # before anything is uploaded
+            dev = f"cuda:{self.device}"
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            check_jacobian_bytes(shape[0], self.n_params, free)
+        t, _ = self._to_dev(x)
+        return t, self._new((t.shape[0], self.n_params))
+
+    def _jac_ws(self, nbytes, device):
+        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
+            self._vjp_ws = self._workspace(nbytes, device)
+        return self._vjp_ws
+
+    def logpdf_jacobian(self, x, return_logp=False):
+        """jac[b, p] = d log_pdf_b / d theta_p -> torch.cuda float32 [B, n_params] (jax.jacrev(log_pdf, argnums=0)(params, batch), vqmc.py:179, in
+        flat leaf order: core.unflatten_batched gives the pytree); with return_logp also log_pdf [B] of the same sweep."""
+        L = _lib.lib()
+        t, jac = self._jac_rows(x)
+        B = t.shape[0]
+        ws = self._jac_ws(_lib.check(L.wf_logpdf_jac_workspace_bytes(self._h, B), "wf_logpdf_jac_workspace_bytes"), t.device)
+        lp = self._new((B,)) if return_logp else None
+        _lib.check(L.wf_logpdf_jac(self._h, self._p(t), B, self._p(jac), self._p(lp), self._p(ws), ws.numel(), self._stream()), "wf_logpdf_jac")
+        return (jac, lp) if return_logp else jac
+
+    def psi_jacobian(self, x, w_psi=None, w_lap=None):
+        """jac[b, p] = w_psi[b] d psi_b / d theta_p + w_lap[b] d laplacian_b / d theta_p -> torch.cuda float32 [B, n_params]: the rows whose sum
+        is psi_vjp.  Defaults w_psi = 1, w_lap = 0: jax.jacrev(psi, argnums=0)(params, batch)."""
+        torch = _torch()
+        L = _lib.lib()
+        t, jac = self._jac_rows(x)
+        B = t.shape[0]
+        wp = torch.ones(B, dtype=torch.float32, device=t.device) if w_psi is None else torch.as_tensor(w_psi, dtype=torch.float32).to(t.device).contiguous()
+        wl = None if w_lap is None else torch.as_tensor(w_lap, dtype=torch.float32).to(t.device).contiguous()
+        if wp.numel() != B or (wl is not None and wl.numel() != B):
+            raise ValueError("w_psi / w_lap must have one entry per walker")
+        ws = self._jac_ws(_lib.check(L.wf_psi_jac_workspace_bytes(self._h, B), "wf_psi_jac_workspace_bytes"), t.device)
+        _lib.check(L.wf_psi_jac(self._h, self._p(t), B, self._p(wp), self._p(wl), self._p(jac), self._p(ws), ws.numel(), self._stream()), "wf_psi_jac")
+        return jac
 
     def logpdf_loss_grad(self, x, weight):
         """(log_pdf [B], weight * sum_b d log_pdf_b / d theta [n_params]) from one forward and one reverse sweep."""

@@ -279,6 +279,54 @@ int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* 
     return launch_zgrad_scatter(m->d_zgrad, m->z_rows, m->d_zmap, m->d_zraw_off, m->d_plain, grad_dev, stream);
 }
 
+// Per-walker Jacobian rows (wf_logpdf_jac, wf_psi_jac): the taped wave sweeps of run_vjp_chunks, then k_wjac instead of k_wgrad + gather.
+// mode 0: log_pdf, every walker seeded with 1 (logp_dev, if given, receives log_pdf of the same forward sweep); mode 1: psi (w1) and its Laplacian
+// (w2, null = zeros).  The workspace holds the tape, the tails, four floats per walker and the zero_params adjoints, laid out as there; jac_dev
+// [B][n_params] is the caller's.  Chunks of what the workspace holds: a row depends on its walker alone, so the chunking changes no bit.
+static int run_jac_chunks(const wf_model* m, int mode, const float* x_dev, int64_t B, const float* w1, const float* w2, float* logp_dev, float* jac_dev,
+                          void* workspace_dev, int64_t workspace_bytes, void* stream) {
+    const bool second_order = mode == 1;
+    const int D = m->desc.n_dim;
+    const int64_t chunk = workspace_bytes / vjp_bytes_per_walker(m, second_order);
+    if (B > 0 && chunk < 1) return WF_ERR_INVALID;
+    DeviceGuard g(m->device);
+    if (B == 0) return WF_OK;
+    const int n_nets = (int)m->nets.size();
+    const int kind = second_order ? m->ring2 : 0;
+    const int64_t samples_per = ring_samples(D, kind), nc = ring_coefs(D, kind);
+    float* tape = (float*)workspace_dev;
+    float* tails = tape + chunk * samples_per * n_nets * grad_ws_rows(D, m->nbp) * nc;
+    float* per_walker = tails + chunk * wave_tail_floats(D, kind);   // [4][chunk]
+    float* zws = m->z_rows ? per_walker + 4 * chunk : nullptr;        // [chunk * samples_per][z_rows]
+    // the flat parameters of each net (leaf order: the nets follow each other and cover the vector)
+    std::vector<int> seg((size_t)n_nets + 1);
+    for (int n = 0; n < n_nets; ++n) seg[(size_t)n] = n == 0 ? 0 : (int)m->nets[(size_t)n].offset;
+    seg[(size_t)n_nets] = (int)m->n_params;
+    for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+        const int64_t bc = std::min(chunk, B - c0);
+        int rc = launch_wave_fwd(m->dev, m->d_dev, kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x_dev + c0 * D, bc, tape, tails, 1, stream);
+        if (rc) return rc;
+        const float *cw1 = w1 ? w1 + c0 : nullptr, *cw2 = w2 ? w2 + c0 : nullptr;
+        if (mode == 0) {   // log_pdf values (to the caller, or to a per-walker slot nobody reads) + the constant seed 1
+            float* wp = per_walker + 2 * chunk;
+            rc = launch_tail_out(m->dev, 0, tails, bc, logp_dev ? logp_dev + c0 : per_walker, nullptr, stream, wp, 1.0f);
+            if (rc) return rc;
+            cw1 = wp;
+        }
+        rc = launch_wave_bwd(m->dev, m->d_dev, mode, kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, bc, cw1, cw2, tape, tails, zws, stream);
+        if (rc) return rc;
+        rc = launch_wjac(D, m->nbp, kind, n_nets, bc, tape, seg.data(), plain_fwd_floats(D, m->nbp), m->d_grad_map, zws ? m->d_zinv : nullptr, zws,
+                         m->z_rows, m->d_zraw_off, m->d_plain, m->n_params, jac_dev + c0 * m->n_params, stream);
+        if (rc) return rc;
+    }
+    return WF_OK;
+}
+// the tape of up to 32768 walkers, as the wave path of vjp_ws_bytes (no matrix-core term: these entries never take that path)
+static int64_t jac_ws_bytes(const wf_model* m, int64_t B, bool second_order) {
+    if (!m || B < 0) return WF_ERR_INVALID;
+    if (!m->d_grad_map || (second_order && !m->grad_psi_ok)) return WF_ERR_UNSUPPORTED;
+    return std::min<int64_t>(std::max<int64_t>(B, 1), 32768) * vjp_bytes_per_walker(m, second_order);
+}
 
 }  // namespace wf
 
@@ -502,6 +550,25 @@ int wf_logpdf_vjp(const wf_model* m, const float* x_dev, int64_t B, const float*
     if (rc) return rc;
     if (B > 0 && (!w_dev || !workspace_dev)) return WF_ERR_INVALID;
     return run_vjp_chunks(m, 0, false, x_dev, B, w_dev, nullptr, nullptr, 0.0f, 0.0f, nullptr, grad_dev, workspace_dev, workspace_bytes, stream);
+}
+
+int64_t wf_psi_jac_workspace_bytes(const wf_model* m, int64_t B) { return jac_ws_bytes(m, B, true); }
+int64_t wf_logpdf_jac_workspace_bytes(const wf_model* m, int64_t B) { return jac_ws_bytes(m, B, false); }
+
+int wf_psi_jac(const wf_model* m, const float* x_dev, int64_t B, const float* w_psi_dev, const float* w_lap_dev, float* jac_dev, void* workspace_dev,
+               int64_t workspace_bytes, void* stream) {
+    int rc = check_grad(m, x_dev, B, jac_dev, true);
+    if (rc) return rc;
+    if (B > 0 && (!w_psi_dev || !workspace_dev)) return WF_ERR_INVALID;
+    return run_jac_chunks(m, 1, x_dev, B, w_psi_dev, w_lap_dev, nullptr, jac_dev, workspace_dev, workspace_bytes, stream);
+}
+
+int wf_logpdf_jac(const wf_model* m, const float* x_dev, int64_t B, float* jac_dev, float* logp_dev, void* workspace_dev, int64_t workspace_bytes,
+                  void* stream) {
+    int rc = check_grad(m, x_dev, B, jac_dev, false);
+    if (rc) return rc;
+    if (B > 0 && !workspace_dev) return WF_ERR_INVALID;
+    return run_jac_chunks(m, 0, x_dev, B, nullptr, nullptr, logp_dev, jac_dev, workspace_dev, workspace_bytes, stream);
 }
 
 int wf_logpdf_loss_grad(const wf_model* m, const float* x_dev, int64_t B, float weight, float* logp_dev, float* grad_dev, void* workspace_dev,

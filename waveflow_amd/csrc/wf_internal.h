@@ -199,6 +199,12 @@ int grad_ws_rows(int D, int nbp);
 int wgrad_partial_floats(int n_nets, int64_t net_img_floats);
 int launch_wgrad(int D, int nbp, int ring_kind, int n_nets, int64_t n_samples, const float* ws, float* partial, int accumulate, float* grad_img,
                  int64_t net_img_floats, int* split_out, void* stream);
+// tape -> per-walker Jacobian rows (k_wjac): jac[b][p] = the product k_wgrad sums over the samples, for the samples of walker b alone, in flat
+// leaf order.  seg[n] .. seg[n + 1]: the flat parameters of net n (seg[0] = 0, seg[n_nets] = n_params); zinv / zws / zraw_off / plain: the
+// zero_params leaves of gated heads (zinv[p] = row of zws, -1 elsewhere; all null for ungated models)
+int launch_wjac(int D, int nbp, int ring_kind, int n_nets, int64_t n_walkers, const float* ws, const int* seg, int64_t net_img_floats,
+                const int32_t* inv, const int32_t* zinv, const float* zws, int z_rows, const int32_t* zraw_off, const float* plain, int64_t n_params,
+                float* jac, void* stream);
 int launch_wave_fwd(const ModelDev& md, const ModelDev* md_dev, int ring_kind, const float* tabI4, const float* tabP4, const float* fk_nat,
                     const float* x, int64_t B, float* ws, float* tails, int taped, void* stream);
 int launch_wave_bwd(const ModelDev& md, const ModelDev* md_dev, int mode, int ring_kind, const float* tabI4, const float* tabP4,

@@ -253,6 +253,73 @@ __global__ void k_zgrad_scatter(const float* __restrict__ zgrad, int n_rows, con
     flat[t] = g;
 }
 
+// ---- per-walker Jacobian rows: k_wgrad's product without the sum over the walkers.  jac[b][p] = sum over the samples s of walker b (its
+// directions in R3, its blocks of directions in RF) and the slots k of X[m][k][s] * Y[n][partner(k)][s], (m, n) the image entry inv[p] of
+// flat parameter p; bias entries: Y[n][NC-1][s].  One workgroup per (walker, net): the walker's tape rows of that net are staged in LDS once,
+// then the threads walk the net's flat parameters, so a wave writes 256 contiguous bytes of the row.  Every p of the net's segment is written
+// (inv[p] < 0: 0, or for the zero_params leaves of a gated head the adjoint the reverse sweep left in zws, with k_zgrad_scatter's sign rule).
+// Plain fp32, a fixed order of additions per entry, no other walker's data: a row is bitwise the same in any batch.
+struct JacSegs {
+    int p0[kMaxNets + 1];   // net n owns the flat parameters p0[n] .. p0[n + 1]
+};
+template <int NC>
+__global__ __launch_bounds__(256) void k_wjac(const float* __restrict__ ws, int n_nets, int dirs, int rows, const WJobs jobs, int net_img_floats,
+                                              const JacSegs segs, const int32_t* __restrict__ inv, const int32_t* __restrict__ zinv,
+                                              const float* __restrict__ zws, int z_rows, const int32_t* __restrict__ zraw_off,
+                                              const float* __restrict__ plain, int64_t n_params, float* __restrict__ jac) {
+    extern __shared__ float4_t tape4[];   // [direction][coefficient][row] of this walker and net
+    const int net = blockIdx.x % n_nets;
+    const int64_t b = blockIdx.x / n_nets;
+    const int tid = threadIdx.x;
+    const int per = NC * rows;   // floats of one (sample, net): a multiple of 4, 16-byte aligned in the tape
+    for (int dir = 0; dir < dirs; ++dir) {
+        const float4_t* __restrict__ src = reinterpret_cast<const float4_t*>(ws + ((b * dirs + dir) * n_nets + net) * (int64_t)per);
+        for (int e = tid; e < per / 4; e += 256) tape4[dir * (per / 4) + e] = src[e];
+    }
+    __syncthreads();
+    const float* __restrict__ tp = reinterpret_cast<const float*>(tape4);
+    float* __restrict__ row = jac + b * n_params;
+    const int img0 = net * net_img_floats;
+    for (int p = segs.p0[net] + tid; p < segs.p0[net + 1]; p += 256) {
+        const int t = inv[p];
+        float v = 0.0f;
+        if (t >= 0) {
+            const int loc = t - img0;
+            int xrow = -1, yrow = 0;   // xrow < 0: a bias entry
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const WJob jb = jobs.j[i];
+                // W0 is [M][64] (sm = 64), W1t and W2t are [N][64] (sn = 64): the inner index is the low 6 bits either way
+                if (loc >= jb.out && loc < jb.out + (jb.sm == 1 ? jb.N : jb.M) * H) {
+                    const int q = loc - jb.out, hi = q >> 6, lo = q & 63;
+                    xrow = jb.xrow + (jb.sm == 1 ? lo : hi);
+                    yrow = jb.yrow + (jb.sm == 1 ? hi : lo);
+                }
+                if (loc >= jb.bias && loc < jb.bias + jb.N) yrow = jb.yrow + (loc - jb.bias);
+            }
+            for (int dir = 0; dir < dirs; ++dir) {
+                const float* __restrict__ q = tp + dir * per;
+                if (xrow < 0) {
+                    v += q[(NC - 1) * rows + yrow];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) v = __builtin_fmaf(q[k * rows + xrow], q[ring_partner(NC, k) * rows + yrow], v);
+                }
+            }
+        } else if (zinv) {
+            const int r = zinv[p];
+            if (r >= 0) {
+                for (int dir = 0; dir < dirs; ++dir) v += zws[(b * dirs + dir) * z_rows + r];
+                if (zraw_off[r] >= 0) {   // d|z|/dz = sign(z), 0 at z = 0
+                    const float raw = plain[zraw_off[r]];
+                    v = raw < 0.0f ? -v : (raw > 0.0f ? v : 0.0f);
+                }
+            }
+        }
+        row[p] = v;
+    }
+}
+
 // ---- Adam as in jax.example_libraries.optimizers.adam (vqmc.py:136), step index i as passed to opt_update
 __global__ void k_adam(float* __restrict__ x, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, float c1, float c2,
                        float step_size, float b1, float b2, float eps, const unsigned long long* __restrict__ step_dev) {
@@ -360,6 +427,30 @@ int run_wgrad(int n_nets, int64_t n_samples, const float* ws, float* partial, in
     return finish();
 }
 
+template <int D, int NC, int NBK = 1>
+int run_wjac(int n_nets, int64_t n_walkers, int dirs, const float* ws, const int* seg, int64_t net_img_floats, const int32_t* inv, const int32_t* zinv,
+             const float* zws, int z_rows, const int32_t* zraw_off, const float* plain, int64_t n_params, float* jac, hipStream_t s) {
+    using R = Rows<D, NBK>;
+    constexpr int W = NBP * NBK;
+    static_assert(R::N % 4 == 0, "the tape rows of a net are staged with 16-byte loads");
+    if (n_nets <= 0 || n_nets > kMaxNets || n_walkers <= 0 || n_params <= 0) return WF_OK;
+    if (n_walkers * n_nets > 0x7fffffff) return WF_ERR_INVALID;
+    // the forward-image layout and the jobs of run_wgrad
+    const int oW0 = 0, ob0 = D * H, oW1 = ob0 + H, ob1 = oW1 + H * H, oW2 = ob1 + H, ob2 = oW2 + D * W * H;
+    WJobs jobs;
+    jobs.j[0] = WJob{R::U, D, R::A1, H, oW0, H, 1, ob0};
+    jobs.j[1] = WJob{R::H1, H, R::A2, H, oW1, 1, H, ob1};
+    jobs.j[2] = WJob{R::H2, H, R::O, D * W, oW2, 1, H, ob2};
+    JacSegs segs{};
+    for (int n = 0; n <= n_nets; ++n) segs.p0[n] = seg[n];
+    static DynLdsSlots cfg;
+    const int lds_bytes = dirs * NC * R::N * (int)sizeof(float);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k_wjac<NC>), lds_bytes, &cfg)) return rc;
+    hipLaunchKernelGGL((k_wjac<NC>), dim3((unsigned)(n_walkers * n_nets)), dim3(256), lds_bytes, s, ws, n_nets, dirs, R::N, jobs,
+                       (int)net_img_floats, segs, inv, zinv, zws, z_rows, zraw_off, plain, n_params, jac);
+    return finish();
+}
+
 }  // namespace
 
 int grad_ws_rows(int D, int nbp) { return 8 + 4 * H + D * nbp; }
@@ -398,6 +489,40 @@ int launch_wgrad(int D, int nbp, int ring_kind, int n_nets, int64_t n_samples, c
         default: return WF_ERR_UNSUPPORTED;
     }
 #undef CALLK
+}
+
+// tape -> Jacobian rows of n_walkers walkers (ring_samples(D, ring_kind) consecutive samples each)
+int launch_wjac(int D, int nbp, int ring_kind, int n_nets, int64_t n_walkers, const float* ws, const int* seg, int64_t net_img_floats,
+                const int32_t* inv, const int32_t* zinv, const float* zws, int z_rows, const int32_t* zraw_off, const float* plain, int64_t n_params,
+                float* jac, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int dirs = ring_samples(D, ring_kind);
+#define ARGS n_nets, n_walkers, dirs, ws, seg, net_img_floats, inv, zinv, zws, z_rows, zraw_off, plain, n_params, jac, s
+#define CALLK(DD, K) return ring_kind == 2 ? run_wjac<DD, rf_block(DD) + 2, K>(ARGS) : ring_kind == 1 ? run_wjac<DD, 3, K>(ARGS) : run_wjac<DD, 1, K>(ARGS)
+    if (nbp == 64) {
+        switch (D) {
+            case 2: CALLK(2, 2);
+            case 3: CALLK(3, 2);
+            case 4: CALLK(4, 2);
+            case 5: CALLK(5, 2);
+            case 6: CALLK(6, 2);
+            case 7: CALLK(7, 2);
+            case 8: CALLK(8, 2);
+            default: return WF_ERR_UNSUPPORTED;
+        }
+    }
+    switch (D) {
+        case 2: CALLK(2, 1);
+        case 3: CALLK(3, 1);
+        case 4: CALLK(4, 1);
+        case 5: CALLK(5, 1);
+        case 6: CALLK(6, 1);
+        case 7: CALLK(7, 1);
+        case 8: CALLK(8, 1);
+        default: return WF_ERR_UNSUPPORTED;
+    }
+#undef CALLK
+#undef ARGS
 }
 
 int launch_zgrad_reduce(const float* zws, int64_t n_samples, int n_rows, int accumulate, float* zpart, float* zgrad, void* stream) {

@@ -117,6 +117,7 @@ struct wf_model {
     float* d_zgrad = nullptr;        // [z_rows]
     int32_t* d_zmap = nullptr;       // row -> index of its leaf entry in the flat vector (-1: padding lane / ungated net)
     int32_t* d_zraw_off = nullptr;   // row -> offset of the raw leaf value in the plain image for |z| heads (-1: signed head)
+    int32_t* d_zinv = nullptr;       // [n_params]: the inverse of d_zmap, -1 for every parameter that is no zero_params entry of a gated head (k_wjac)
 };
 
 namespace wf {

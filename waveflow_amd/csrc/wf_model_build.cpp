@@ -530,6 +530,13 @@ static int grad_prepare(wf_model* m) {
         rc = dev_alloc(m, &m->d_zraw_off, zoff.size());
         if (rc) return rc;
         WF_HIP(hipMemcpy(m->d_zraw_off, zoff.data(), zoff.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        // the inverse, over the flat vector: what the per-walker Jacobian (k_wjac) walks
+        std::vector<int32_t> zinv((size_t)std::max<int64_t>(m->n_params, 1), -1);
+        for (size_t r = 0; r < zmap.size(); ++r)
+            if (zmap[r] >= 0) zinv[(size_t)zmap[r]] = (int32_t)r;
+        rc = dev_alloc(m, &m->d_zinv, zinv.size());
+        if (rc) return rc;
+        WF_HIP(hipMemcpy(m->d_zinv, zinv.data(), zinv.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         rc = dev_alloc(m, &m->d_zpart, (size_t)64 * m->z_rows);
         if (rc) return rc;
         rc = dev_alloc(m, &m->d_zgrad, (size_t)m->z_rows);

@@ -16,7 +16,7 @@ from pathlib import Path
 import numpy as np
 
 from . import checkpoint
-from .core import DeviceParams, flatten_params
+from .core import DeviceParams, flatten_params, unflatten_batched
 from .model_factory import get_waveflow_model
 from .utils import helpers, physics
 
@@ -218,6 +218,33 @@ def train_step(epoch, psi, h_fn, log_pdf, opt_update, opt_state, get_params, bat
     """vqmc.py:169-187 -> (new opt_state, loss)"""
     gradients, loss_val = train_step_gradients(get_params(opt_state), psi, h_fn, log_pdf, batch, running_average, group=group)
     return opt_update(epoch, gradients, opt_state), loss_val
+
+
+def log_pdf_jacobian(log_pdf):
+    """-> jac(params, batch): jax.jacrev(log_pdf, argnums=0)(params, batch) (vqmc.py:179), the pytree of `params` with a leading batch axis on
+    every leaf (float32 cuda views of one [B, n_params] tensor).  train_step keeps its contracted path (logpdf_vjp)."""
+    model = log_pdf.model
+
+    def jac(params, batch):
+        model.ensure_params(params)
+        return unflatten_batched(params, model.logpdf_jacobian(batch))
+    jac.model = model
+    return jac
+
+
+def log_psi_jacobian(psi):
+    """-> jac(params, batch): O_k(x_b) = d ln psi_b / d theta_k as jacrev(psi) / (psi + 1e-8) -- the reference's regulariser (vqmc.py:196) --,
+    the pytree of `params` with a leading batch axis: the rows stochastic reconfiguration and per-sample gradient statistics start from."""
+    model = psi.model
+
+    def jac(params, batch):
+        model.ensure_params(params)
+        x, _ = model._to_dev(batch)
+        rows = model.psi_jacobian(x)
+        rows /= (model.psi(x) + 1e-8)[:, None]
+        return unflatten_batched(params, rows)
+    jac.model = model
+    return jac
 
 
 def _save_optimizer_state(save_dir, opt_state, epoch):
