@@ -23,6 +23,54 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().wf_abi_version() == 2     # round 2: gate flags and the coupling-stack fields appended to wf_model_desc
 
 
+def _header_prototypes():
+    """name -> (class of the return type, [class per argument]) for every wf_* function the header declares, in its order."""
+    hdr = open(os.path.join(ROOT, "include", "waveflow_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    scalar = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "f32"}
+
+    def c_class(text, is_return=False):
+        words = [w for w in text.replace("*", " * ").split() if w != "const"]
+        if "*" in words:
+            return "string" if is_return and words[0] == "char" else "pointer"
+        if is_return and words == ["void"]:
+            return "void"
+        return scalar[words[0]]   # KeyError: a type this test does not know
+
+    out = {}
+    for ret, name, args in re.findall(r"^([\w \*]+?)\b(wf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr, flags=re.M):
+        args = [a.strip() for a in args.split(",")]
+        assert name not in out, name
+        out[name] = (c_class(ret, True), [] if args == ["void"] else [c_class(a.rsplit(None, 1)[0] if "*" not in a else a) for a in args])
+    return out
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_void_p: "pointer", ctypes.c_char_p: "string", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64",
+            ctypes.c_float: "f32"}[t]
+
+
+def test_prototype_table_matches_the_header():
+    """_lib.PROTOTYPES against include/waveflow_hip.h: the same functions in the same order, the same number of arguments, and per position
+    (and for the return value) the same class: pointer, 32-bit int, 64-bit int, unsigned 64-bit, float; const char* is c_char_p, void is None."""
+    declared = _header_prototypes()
+    assert len(declared) == 55 and list(declared) == list(_lib.PROTOTYPES) == _lib.EXPORTS
+    L = _lib.lib()
+    for name, (ret, args) in declared.items():
+        restype, argtypes = _lib.PROTOTYPES[name]
+        assert len(argtypes) == len(args), (name, len(argtypes), len(args))
+        assert [_ctypes_class(t) for t in argtypes] == args, (name, args)
+        assert _ctypes_class(restype) == ret, (name, ret)
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes) == list(argtypes), name   # lib() applies the table, all of it
+    assert [n for n, (_, a) in declared.items() if not a] == ["wf_abi_version", "wf_last_hip_error", "wf_last_hip_error_string", "wf_device_count"]
+    assert ctypes.sizeof(ctypes.c_int) == 4 and ctypes.sizeof(ctypes.c_float) == 4
+
+
 def test_desc_struct_matches_header_layout():
     # 4-byte fields only; guards against drift between _lib.ModelDesc and wf_model_desc
     assert ctypes.sizeof(_lib.BC) == 4 + 4 * 4 + 4 * 4

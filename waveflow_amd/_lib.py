@@ -70,17 +70,69 @@ class TrainState(ctypes.Structure):
                 ("running_average_dev", ctypes.c_void_p), ("loss_ring_dev", ctypes.c_void_p), ("ring_len", ctypes.c_int32), ("defer_eval_tables", ctypes.c_int32)]
 
 
-EXPORTS = ["wf_abi_version", "wf_strerror", "wf_last_hip_error", "wf_last_hip_error_string", "wf_device_count",
-           "wf_tables_build", "wf_model_create", "wf_model_destroy", "wf_model_param_count", "wf_model_n_bases",
-           "wf_model_set_params", "wf_model_set_kernel", "wf_logpdf_fwd", "wf_psi_fwd", "wf_flow_fwd", "wf_layer_fwd",
-           "wf_block_sums", "wf_block_sums_workspace_bytes", "wf_rqs_fwd", "wf_inverse_fwd", "wf_sample", "wf_hamiltonian_fwd",
-           "wf_psi_vjp", "wf_psi_vjp_workspace_bytes", "wf_vqmc_seeds",
-           "wf_logpdf_vjp", "wf_logpdf_vjp_workspace_bytes", "wf_vqmc_loss_grad", "wf_model_set_params_device", "wf_adam_step",
-           "wf_vqmc_train_step", "wf_vqmc_train_step_workspace_bytes", "wf_nsc_fwd", "wf_nsc_workspace_bytes", "wf_logpdf_loss_grad", "wf_mle_train_step", "wf_mle_train_step_workspace_bytes", "wf_vqmc_train_step_local",
-           "wf_vqmc_train_step_apply", "wf_psi_antisym_fwd", "wf_logpdf_unsorted_fwd", "wf_inversion_count",
-           "wf_spline_create", "wf_spline_destroy", "wf_spline_n_bases", "wf_spline_apply", "wf_spline_reverse", "wf_spline_enforce_bc",
-           "wf_spline_remove_bias", "wf_spline_sample", "wf_psi_coord_derivs",
-           "wf_logpdf_jac", "wf_logpdf_jac_workspace_bytes", "wf_psi_jac", "wf_psi_jac_workspace_bytes"]
+_vp, _i32, _i64, _u64, _f32, _str = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_char_p
+_ws = [_vp, _i64]          # (workspace_dev, workspace_bytes)
+_adam = [_f32] * 4         # (step_size, b1, b2, eps)
+_state = ctypes.POINTER(TrainState)
+# name -> (restype, argtypes): every function of include/waveflow_hip.h, in its order (tests/test_abi_host.py holds the two against each other)
+PROTOTYPES = {
+    "wf_tables_build": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "wf_strerror": (_str, [_i32]),
+    "wf_abi_version": (_i32, []),
+    "wf_last_hip_error": (_i32, []),
+    "wf_last_hip_error_string": (_str, []),
+    "wf_device_count": (_i32, []),
+    "wf_model_create": (_i32, [ctypes.POINTER(ModelDesc), _i32, ctypes.POINTER(_vp)]),
+    "wf_model_destroy": (None, [_vp]),
+    "wf_model_param_count": (_i64, [_vp]),
+    "wf_model_n_bases": (_i32, [_vp, _i32]),
+    "wf_model_set_params": (_i32, [_vp, _vp, _i64, _vp]),
+    "wf_model_set_params_device": (_i32, [_vp, _vp, _i64, _vp]),
+    "wf_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64] + _adam + [_vp]),
+    "wf_model_set_kernel": (_i32, [_vp, _i32]),
+    "wf_logpdf_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "wf_psi_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "wf_psi_antisym_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "wf_logpdf_unsorted_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "wf_inversion_count": (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    "wf_flow_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "wf_layer_fwd": (_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "wf_inverse_fwd": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp]),
+    "wf_sample": (_i32, [_vp, _u64, _i64, _vp, _vp, _i32, _vp]),
+    "wf_hamiltonian_fwd": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "wf_psi_coord_derivs": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "wf_psi_vjp_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_psi_vjp": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp] + _ws + [_vp]),
+    "wf_vqmc_loss_grad": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp] + _ws + [_vp]),
+    "wf_vqmc_train_step_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_vqmc_train_step": (_i32, [_vp, _state, _u64, _i64, _vp, _i32] + _adam + [_i32] + _ws + [_vp]),
+    "wf_vqmc_train_step_local": (_i32, [_vp, _state, _u64, _i64, _vp, _i32, _f32, _i32, _vp] + _ws + [_vp]),
+    "wf_vqmc_train_step_apply": (_i32, [_vp, _state, _vp] + _adam + [_vp]),
+    "wf_mle_train_step_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_mle_train_step": (_i32, [_vp, _state, _vp, _i64] + _adam + _ws + [_vp]),
+    "wf_logpdf_vjp_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_logpdf_vjp": (_i32, [_vp, _vp, _i64, _vp, _vp] + _ws + [_vp]),
+    "wf_logpdf_jac_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_logpdf_jac": (_i32, [_vp, _vp, _i64, _vp, _vp] + _ws + [_vp]),
+    "wf_psi_jac_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_psi_jac": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp] + _ws + [_vp]),
+    "wf_logpdf_loss_grad": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp] + _ws + [_vp]),
+    "wf_vqmc_seeds": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "wf_rqs_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "wf_nsc_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "wf_nsc_fwd": (_i32, [_vp, _i64, _i32, _i32, _f32, _i32, _vp, _i32, _vp, _vp] + _ws + [_vp]),
+    "wf_block_sums": (_i32, [_vp, _i64, _vp] + _ws + [_vp]),
+    "wf_block_sums_workspace_bytes": (_i64, [_i64]),
+    "wf_spline_create": (_i32, [ctypes.POINTER(SplineDesc), _vp, _vp, _i32, ctypes.POINTER(_vp)]),
+    "wf_spline_destroy": (None, [_vp]),
+    "wf_spline_n_bases": (_i32, [_vp]),
+    "wf_spline_apply": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "wf_spline_reverse": (_i32, [_vp, _vp, _i64, _vp, _f32, _vp, _vp]),
+    "wf_spline_enforce_bc": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "wf_spline_remove_bias": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "wf_spline_sample": (_i32, [_vp, _u64, _vp, _i64, _i32, _i32, _vp, _vp]),
+}
+EXPORTS = list(PROTOTYPES)
 
 _lib = None
 
@@ -99,116 +151,10 @@ def lib():
         import sys
         print(f"waveflow_amd: experiment library {LIB_PATH}", file=sys.stderr)
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    L.wf_abi_version.restype = i32
-    L.wf_strerror.restype = ctypes.c_char_p
-    L.wf_strerror.argtypes = [i32]
-    L.wf_last_hip_error.restype = i32
-    L.wf_last_hip_error_string.restype = ctypes.c_char_p
-    L.wf_device_count.restype = i32
-    L.wf_tables_build.restype = i32
-    L.wf_tables_build.argtypes = [i32, i32, i32, i32, vp, vp, vp]
-    L.wf_model_create.restype = i32
-    L.wf_model_create.argtypes = [ctypes.POINTER(ModelDesc), i32, ctypes.POINTER(vp)]
-    L.wf_model_destroy.restype = None
-    L.wf_model_destroy.argtypes = [vp]
-    L.wf_model_param_count.restype = i64
-    L.wf_model_param_count.argtypes = [vp]
-    L.wf_model_n_bases.restype = i32
-    L.wf_model_n_bases.argtypes = [vp, i32]
-    L.wf_model_set_params.restype = i32
-    L.wf_model_set_params.argtypes = [vp, f32p, i64, vp]
-    L.wf_model_set_kernel.restype = i32
-    L.wf_model_set_kernel.argtypes = [vp, i32]
-    for name in ("wf_logpdf_fwd", "wf_psi_fwd"):
+    for name, (restype, argtypes) in PROTOTYPES.items():
         f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, i64, vp, vp, vp, vp]
-    L.wf_flow_fwd.restype = i32
-    L.wf_flow_fwd.argtypes = [vp, vp, i64, vp, vp, vp]
-    L.wf_psi_antisym_fwd.restype = i32
-    L.wf_psi_antisym_fwd.argtypes = [vp, vp, i64, vp, vp, vp]
-    L.wf_logpdf_unsorted_fwd.restype = i32
-    L.wf_logpdf_unsorted_fwd.argtypes = [vp, vp, i64, vp, vp]
-    L.wf_inversion_count.restype = i32
-    L.wf_inversion_count.argtypes = [vp, i64, i32, vp, vp]
-    L.wf_layer_fwd.restype = i32
-    L.wf_layer_fwd.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp]
-    L.wf_inverse_fwd.restype = i32
-    L.wf_inverse_fwd.argtypes = [vp, vp, i64, vp, i32, vp]
-    L.wf_sample.restype = i32
-    L.wf_sample.argtypes = [vp, ctypes.c_uint64, i64, vp, vp, i32, vp]
-    L.wf_hamiltonian_fwd.restype = i32
-    L.wf_hamiltonian_fwd.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp]
-    L.wf_psi_coord_derivs.restype = i32
-    L.wf_psi_coord_derivs.argtypes = [vp, vp, i64, vp, vp, vp, vp]
-    L.wf_psi_vjp_workspace_bytes.restype = i64
-    L.wf_psi_vjp_workspace_bytes.argtypes = [vp, i64]
-    L.wf_psi_vjp.restype = i32
-    L.wf_psi_vjp.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.wf_logpdf_vjp_workspace_bytes.restype = i64
-    L.wf_logpdf_vjp_workspace_bytes.argtypes = [vp, i64]
-    L.wf_logpdf_vjp.restype = i32
-    L.wf_logpdf_vjp.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
-    for name in ("wf_logpdf_jac_workspace_bytes", "wf_psi_jac_workspace_bytes"):
-        f = getattr(L, name)
-        f.restype = i64
-        f.argtypes = [vp, i64]
-    L.wf_logpdf_jac.restype = i32
-    L.wf_logpdf_jac.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
-    L.wf_psi_jac.restype = i32
-    L.wf_psi_jac.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.wf_model_set_params_device.restype = i32
-    L.wf_model_set_params_device.argtypes = [vp, vp, i64, vp]
-    L.wf_adam_step.restype = i32
-    L.wf_adam_step.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
-    L.wf_vqmc_train_step_workspace_bytes.restype = i64
-    L.wf_vqmc_train_step_workspace_bytes.argtypes = [vp, i64]
-    L.wf_vqmc_train_step.restype = i32
-    L.wf_vqmc_train_step.argtypes = [vp, ctypes.POINTER(TrainState), ctypes.c_uint64, i64, vp, i32, ctypes.c_float, ctypes.c_float,
-                                     ctypes.c_float, ctypes.c_float, i32, vp, i64, vp]
-    L.wf_nsc_workspace_bytes.restype = i64
-    L.wf_nsc_workspace_bytes.argtypes = [i64, i32, i32]
-    L.wf_nsc_fwd.restype = i32
-    L.wf_nsc_fwd.argtypes = [vp, i64, i32, i32, ctypes.c_float, i32, vp, i32, vp, vp, vp, i64, vp]
-    L.wf_vqmc_train_step_local.restype = i32
-    L.wf_vqmc_train_step_local.argtypes = [vp, ctypes.POINTER(TrainState), ctypes.c_uint64, i64, vp, i32, ctypes.c_float, i32, vp, vp, i64, vp]
-    L.wf_vqmc_train_step_apply.restype = i32
-    L.wf_vqmc_train_step_apply.argtypes = [vp, ctypes.POINTER(TrainState), vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
-    L.wf_mle_train_step_workspace_bytes.restype = i64
-    L.wf_mle_train_step_workspace_bytes.argtypes = [vp, i64]
-    L.wf_mle_train_step.restype = i32
-    L.wf_mle_train_step.argtypes = [vp, ctypes.POINTER(TrainState), vp, i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                    vp, i64, vp]
-    L.wf_logpdf_loss_grad.restype = i32
-    L.wf_logpdf_loss_grad.argtypes = [vp, vp, i64, ctypes.c_float, vp, vp, vp, i64, vp]
-    L.wf_vqmc_loss_grad.restype = i32
-    L.wf_vqmc_loss_grad.argtypes = [vp, vp, i64, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, i64, vp]
-    L.wf_vqmc_seeds.restype = i32
-    L.wf_vqmc_seeds.argtypes = [vp, i64, i32, vp, i32, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]
-    L.wf_rqs_fwd.restype = i32
-    L.wf_rqs_fwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                             vp, vp, vp, vp]
-    L.wf_block_sums.restype = i32
-    L.wf_block_sums.argtypes = [vp, i64, vp, vp, i64, vp]
-    L.wf_block_sums_workspace_bytes.restype = i64
-    L.wf_block_sums_workspace_bytes.argtypes = [i64]
-    L.wf_spline_create.restype = i32
-    L.wf_spline_create.argtypes = [ctypes.POINTER(SplineDesc), vp, vp, i32, ctypes.POINTER(vp)]
-    L.wf_spline_destroy.restype = None
-    L.wf_spline_destroy.argtypes = [vp]
-    L.wf_spline_n_bases.restype = i32
-    L.wf_spline_n_bases.argtypes = [vp]
-    L.wf_spline_apply.restype = i32
-    L.wf_spline_apply.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp]
-    L.wf_spline_reverse.restype = i32
-    L.wf_spline_reverse.argtypes = [vp, vp, i64, vp, ctypes.c_float, vp, vp]
-    for name in ("wf_spline_enforce_bc", "wf_spline_remove_bias"):
-        f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, i64, i32, vp, vp]
-    L.wf_spline_sample.restype = i32
-    L.wf_spline_sample.argtypes = [vp, ctypes.c_uint64, vp, i64, i32, i32, vp, vp]
+        f.restype = restype
+        f.argtypes = argtypes
     if L.wf_abi_version() != 2:
         raise ImportError("libwaveflow_hip ABI version mismatch")
     _lib = L
@@ -219,3 +165,19 @@ def check(status, what):
     if status < 0:
         raise WfError(status, what)
     return status
+
+
+def call(name, *args):
+    """One library call, checked: the entry's status or value (a byte count, a basis count), WfError when it is negative."""
+    return check(getattr(lib(), name)(*args), name)
+
+
+def ptr(t):
+    """Device pointer of a torch tensor; NULL for None and for an empty tensor."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
+
+
+def stream_ptr(device=None):
+    """torch's current HIP stream on `device` (default: the current device) as the `stream` argument."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

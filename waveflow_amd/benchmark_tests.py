@@ -10,7 +10,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib, flows
+from . import flows
 from .model_factory import get_masked_transform
 from .utils import helpers
 from .vqmc import adam
@@ -108,8 +108,7 @@ def train_model(target, num_epochs, n_model_sample, model_type='IFlow', dataset_
     ring = 256
     st = model.make_train_state(state.x, state.m, state.v, 1, ring_len=ring, defer_eval_tables=True)   # refreshed before every evaluation below
     model.set_params_device(state.x)
-    nbytes = _lib.check(_lib.lib().wf_mle_train_step_workspace_bytes(model._h, int(x_dev.shape[0])), "wf_mle_train_step_workspace_bytes")
-    st["ws"] = model._workspace(nbytes, x_dev.device)
+    st["ws"] = model._workspace(model.mle_train_step_workspace_bytes(x_dev.shape[0]), x_dev.device)
     side = torch.cuda.Stream(device=model.device)
     side.wait_stream(torch.cuda.current_stream(model.device))
     with torch.cuda.stream(side):

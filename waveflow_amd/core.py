@@ -97,7 +97,6 @@ class DeviceModel:
 
     def __init__(self, desc, device=None):
         torch = _torch()
-        L = _lib.lib()
         if not torch.cuda.is_available():
             raise _lib.WfError(_lib.ERR_NO_DEVICE, "wf_model_create")
         if device is None:
@@ -105,14 +104,13 @@ class DeviceModel:
         self.device = int(device)
         self.desc = desc
         h = ctypes.c_void_p()
-        _lib.check(L.wf_model_create(ctypes.byref(desc), self.device, ctypes.byref(h)), "wf_model_create")
+        _lib.call("wf_model_create", ctypes.byref(desc), self.device, ctypes.byref(h))
         self._h = h
-        self.n_params = int(L.wf_model_param_count(h))
-        self.i_nb = int(L.wf_model_n_bases(h, 0))
-        self.p_nb = int(L.wf_model_n_bases(h, 1))
-        self._flat = None
+        self.n_params = int(_lib.call("wf_model_param_count", h))
+        self.i_nb = int(_lib.call("wf_model_n_bases", h, 0))
+        self.p_nb = int(_lib.call("wf_model_n_bases", h, 1))
         self._vjp_ws = None
-        self._dev_key = None
+        self._invalidate_host_copy()
         self.D = int(desc.n_dim)
         self.n_layers = int(desc.n_flow_layers)
 
@@ -130,7 +128,7 @@ class DeviceModel:
         flat = np.ascontiguousarray(flat, dtype=np.float32).reshape(-1)
         if flat.size != self.n_params:
             raise ValueError(f"expected {self.n_params} parameters, got {flat.size}")
-        _lib.check(_lib.lib().wf_model_set_params(self._h, flat.ctypes.data, flat.size, self._stream()), "wf_model_set_params")
+        self._run("wf_model_set_params", flat.ctypes.data, flat.size)
         self._flat = flat.copy()
 
     def set_params_device(self, flat_dev):
@@ -138,8 +136,7 @@ class DeviceModel:
         if flat_dev.numel() != self.n_params or str(flat_dev.dtype) != "torch.float32" or not flat_dev.is_cuda:
             raise ValueError(f"expected a float32 cuda vector of {self.n_params} parameters")
         flat_dev = flat_dev.contiguous()
-        _lib.check(_lib.lib().wf_model_set_params_device(self._h, self._p(flat_dev), flat_dev.numel(), self._stream()),
-                   "wf_model_set_params_device")
+        self._run("wf_model_set_params_device", self._p(flat_dev), flat_dev.numel())
         self._flat = None
 
     def ensure_params(self, tree):
@@ -155,14 +152,22 @@ class DeviceModel:
         if self._flat is None or flat.size != self._flat.size or not np.array_equal(flat, self._flat):
             self.set_params(flat)
 
+    def _invalidate_host_copy(self):
+        """The device parameters are no longer what set_params / ensure_params last uploaded (a training step moved them)."""
+        self._flat = None
+        self._dev_key = None
+
     def set_kernel(self, kind):
         kind = {"auto": _lib.KERNEL_AUTO, "scalar": _lib.KERNEL_SCALAR, "mfma": _lib.KERNEL_MFMA, "wave": _lib.KERNEL_WAVE}.get(kind, kind)
-        _lib.check(_lib.lib().wf_model_set_kernel(self._h, int(kind)), "wf_model_set_kernel")
+        _lib.call("wf_model_set_kernel", self._h, int(kind))
 
     # ---- plumbing
     def _stream(self):
-        torch = _torch()
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
+
+    def _run(self, name, *args):
+        """wf_<name>(model, args..., stream), checked."""
+        return _lib.call(name, self._h, *args, self._stream())
 
     def _to_dev(self, x):
         """-> (float32 contiguous cuda tensor [B, D], converter for outputs)"""
@@ -182,12 +187,53 @@ class DeviceModel:
         torch = _torch()
         return torch.empty(shape, device=f"cuda:{self.device}", dtype=dtype or torch.float32)
 
+    _p = staticmethod(_lib.ptr)
+
     @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
+    def _pick(back, *outs):
+        """The outputs that were asked for (the others are None), converted: one value, or a tuple of them."""
+        res = [back(o) for o in outs if o is not None]
+        return res[0] if len(res) == 1 else tuple(res)
+
+    @staticmethod
+    def _protons(protons):
+        """1-D proton positions -> (float32 host pointer or None, n); the pointer object keeps its array alive."""
+        pr = np.ascontiguousarray(np.asarray(protons, dtype=np.float32).reshape(-1))
+        return (pr.ctypes.data_as(ctypes.c_void_p) if pr.size else None), pr.size
+
+    @staticmethod
+    def _weights(w, B, device, message):
+        """A per-walker weight as a float32 cuda vector of B entries, or ValueError(message)."""
+        torch = _torch()
+        t = torch.as_tensor(w, dtype=torch.float32).to(device).contiguous()
+        if t.numel() != B:
+            raise ValueError(message)
+        return t
+
+    @staticmethod
+    def _workspace(nbytes, device):
+        torch = _torch()
+        ws = torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+        if os.environ.get("WF_POISON"):
+            ws.fill_(0xFF)   # NaN patterns: see dev_alloc_bytes in wf_runtime.cpp
+        return ws
+
+    def _grad_ws(self, entry, B, device):
+        """-> (pointer, bytes) of the one workspace all gradient and Jacobian entries share, holding at least what `entry`
+        (a *_workspace_bytes function) asks for B walkers: grown when it is too small, never shrunk."""
+        nbytes = _lib.call(entry, self._h, B)
+        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
+            self._vjp_ws = self._workspace(nbytes, device)
+        return self._p(self._vjp_ws), self._vjp_ws.numel()
+
+    def _train_ws(self, st, nbytes):
+        """-> (pointer, bytes) of the train state's workspace, allocated here unless the caller did (before a capture)."""
+        if st.get("ws") is None or st["ws"].numel() < nbytes:
+            st["ws"] = self._workspace(nbytes, st["x"].device)
+        return self._p(st["ws"]), st["ws"].numel()
 
     # ---- hot path
-    def _eval(self, fn, x, return_sample, return_bin_idx):
+    def _eval(self, name, x, return_sample, return_bin_idx):
         torch = _torch()
         t, back = self._to_dev(x)
         B = t.shape[0]
@@ -196,19 +242,14 @@ class DeviceModel:
         idx = self._new((B, self.n_layers + 1, self.D, 2), torch.int32) if return_bin_idx else None
         if idx is not None:
             idx.zero_()
-        _lib.check(fn(self._h, self._p(t), B, self._p(out), self._p(u), self._p(idx), self._stream()), fn.__name__)
-        res = [back(out)]
-        if return_sample:
-            res.append(back(u))
-        if return_bin_idx:
-            res.append(back(idx))
-        return res[0] if len(res) == 1 else tuple(res)
+        self._run(name, self._p(t), B, self._p(out), self._p(u), self._p(idx))
+        return self._pick(back, out, u, idx)
 
     def log_pdf(self, x, return_sample=False, return_bin_idx=False):
-        return self._eval(_lib.lib().wf_logpdf_fwd, x, return_sample, return_bin_idx)
+        return self._eval("wf_logpdf_fwd", x, return_sample, return_bin_idx)
 
     def psi(self, x, return_sample=False, return_bin_idx=False):
-        return self._eval(_lib.lib().wf_psi_fwd, x, return_sample, return_bin_idx)
+        return self._eval("wf_psi_fwd", x, return_sample, return_bin_idx)
 
     def psi_antisym(self, x, return_inversions=False):
         """psi(sort(x)) * (-1)^inversions(x) for walkers in any particle order (helpers.py:55-58, coordinates.py:41-51): sort and sign on the device."""
@@ -217,22 +258,22 @@ class DeviceModel:
         B = t.shape[0]
         out = self._new((B,))
         inv = self._new((B,), torch.int32) if return_inversions else None
-        _lib.check(_lib.lib().wf_psi_antisym_fwd(self._h, self._p(t), B, self._p(out), self._p(inv), self._stream()), "wf_psi_antisym_fwd")
-        return (back(out), back(inv)) if return_inversions else back(out)
+        self._run("wf_psi_antisym_fwd", self._p(t), B, self._p(out), self._p(inv))
+        return self._pick(back, out, inv)
 
     def log_pdf_unsorted(self, x):
         """log_pdf(sort(x)): rows in any particle order, sorted on the device."""
         t, back = self._to_dev(x)
         B = t.shape[0]
         out = self._new((B,))
-        _lib.check(_lib.lib().wf_logpdf_unsorted_fwd(self._h, self._p(t), B, self._p(out), self._stream()), "wf_logpdf_unsorted_fwd")
+        self._run("wf_logpdf_unsorted_fwd", self._p(t), B, self._p(out))
         return back(out)
 
     def flow(self, x):
         t, back = self._to_dev(x)
         B = t.shape[0]
         u, ld = self._new((B, self.D)), self._new((B,))
-        _lib.check(_lib.lib().wf_flow_fwd(self._h, self._p(t), B, self._p(u), self._p(ld), self._stream()), "wf_flow_fwd")
+        self._run("wf_flow_fwd", self._p(t), B, self._p(u), self._p(ld))
         return back(u), back(ld)
 
     def layer(self, l, u_in, return_bin_idx=False):
@@ -243,18 +284,15 @@ class DeviceModel:
         idx = self._new((B, self.D, 2), torch.int32) if return_bin_idx else None
         if idx is not None:
             idx.zero_()
-        _lib.check(_lib.lib().wf_layer_fwd(self._h, int(l), self._p(t), B, self._p(y), self._p(ld), self._p(idx), self._stream()),
-                   "wf_layer_fwd")
-        if return_bin_idx:
-            return back(y), back(ld), back(idx)
-        return back(y), back(ld)
+        self._run("wf_layer_fwd", int(l), self._p(t), B, self._p(y), self._p(ld), self._p(idx))
+        return self._pick(back, y, ld, idx)
 
     def inverse(self, u, exact=False):
         """Serial.inverse_fun; exact=False reproduces the reference's IMADE.inverse_fun (conditioner on its inputs)."""
         t, back = self._to_dev(u)
         B = t.shape[0]
         x = self._new((B, self.D))
-        _lib.check(_lib.lib().wf_inverse_fwd(self._h, self._p(t), B, self._p(x), int(bool(exact)), self._stream()), "wf_inverse_fwd")
+        self._run("wf_inverse_fwd", self._p(t), B, self._p(x), int(bool(exact)))
         return back(x)
 
     def sample(self, seed, num_samples, return_latent=False, exact=False):
@@ -262,26 +300,18 @@ class DeviceModel:
         B = int(num_samples)
         x = self._new((B, self.D))
         lat = self._new((B, self.D)) if return_latent else None
-        _lib.check(_lib.lib().wf_sample(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), B, self._p(x), self._p(lat),
-                                        int(bool(exact)), self._stream()), "wf_sample")
+        self._run("wf_sample", ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), B, self._p(x), self._p(lat), int(bool(exact)))
         return (x, lat) if return_latent else x
 
     def hamiltonian(self, x, protons, return_psi=False, return_laplacian=False):
         """H psi = -1/2 laplacian(psi) + V psi (physics.construct_hamiltonian_function); protons: 1-D positions."""
         t, back = self._to_dev(x)
         B = t.shape[0]
-        pr = np.ascontiguousarray(np.asarray(protons, dtype=np.float32).reshape(-1))
         h = self._new((B,))
         ps = self._new((B,)) if return_psi else None
         lap = self._new((B,)) if return_laplacian else None
-        _lib.check(_lib.lib().wf_hamiltonian_fwd(self._h, self._p(t), B, pr.ctypes.data if pr.size else None, pr.size, self._p(h),
-                                                 self._p(ps), self._p(lap), self._stream()), "wf_hamiltonian_fwd")
-        res = [back(h)]
-        if return_psi:
-            res.append(back(ps))
-        if return_laplacian:
-            res.append(back(lap))
-        return res[0] if len(res) == 1 else tuple(res)
+        self._run("wf_hamiltonian_fwd", self._p(t), B, *self._protons(protons), self._p(h), self._p(ps), self._p(lap))
+        return self._pick(back, h, ps, lap)
 
     def psi_derivatives(self, x, hessian_diag=False, return_psi=False):
         """d psi / d x_d -> [B, D] (jax.grad(psi, 1)); with hessian_diag also d^2 psi / d x_d^2 -> [B, D] (the diagonal of jax.hessian(psi, 1),
@@ -291,48 +321,28 @@ class DeviceModel:
         grad = self._new((B, self.D))
         hd = self._new((B, self.D)) if hessian_diag else None
         ps = self._new((B,)) if return_psi else None
-        _lib.check(_lib.lib().wf_psi_coord_derivs(self._h, self._p(t), B, self._p(ps), self._p(grad), self._p(hd), self._stream()),
-                   "wf_psi_coord_derivs")
-        res = [back(grad)]
-        if hessian_diag:
-            res.append(back(hd))
-        if return_psi:
-            res.append(back(ps))
-        return res[0] if len(res) == 1 else tuple(res)
+        self._run("wf_psi_coord_derivs", self._p(t), B, self._p(ps), self._p(grad), self._p(hd))
+        return self._pick(back, grad, hd, ps)
 
     def psi_vjp(self, x, w_psi, w_lap):
         """grad[p] = sum_b (w_psi[b] d psi_b/d theta_p + w_lap[b] d laplacian_b/d theta_p) -> torch.cuda float32 [n_params]."""
-        torch = _torch()
-        L = _lib.lib()
         t, _ = self._to_dev(x)
         B = t.shape[0]
-        wp = torch.as_tensor(w_psi, dtype=torch.float32).to(t.device).contiguous()
-        wl = torch.as_tensor(w_lap, dtype=torch.float32).to(t.device).contiguous()
-        if wp.numel() != B or wl.numel() != B:
-            raise ValueError("w_psi / w_lap must have one entry per walker")
-        nbytes = _lib.check(L.wf_psi_vjp_workspace_bytes(self._h, B), "wf_psi_vjp_workspace_bytes")
-        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
-            self._vjp_ws = self._workspace(nbytes, t.device)
+        wp = self._weights(w_psi, B, t.device, "w_psi / w_lap must have one entry per walker")
+        wl = self._weights(w_lap, B, t.device, "w_psi / w_lap must have one entry per walker")
+        ws = self._grad_ws("wf_psi_vjp_workspace_bytes", B, t.device)
         grad = self._new((self.n_params,))
-        _lib.check(L.wf_psi_vjp(self._h, self._p(t), B, self._p(wp), self._p(wl), self._p(grad), self._p(self._vjp_ws),
-                                self._vjp_ws.numel(), self._stream()), "wf_psi_vjp")
+        self._run("wf_psi_vjp", self._p(t), B, self._p(wp), self._p(wl), self._p(grad), *ws)
         return grad
 
     def logpdf_vjp(self, x, w):
         """grad[p] = sum_b w[b] d log_pdf_b / d theta_p -> torch.cuda float32 [n_params]."""
-        torch = _torch()
-        L = _lib.lib()
         t, _ = self._to_dev(x)
         B = t.shape[0]
-        wt = torch.as_tensor(w, dtype=torch.float32).to(t.device).contiguous()
-        if wt.numel() != B:
-            raise ValueError("w must have one entry per row of x")
-        nbytes = _lib.check(L.wf_logpdf_vjp_workspace_bytes(self._h, B), "wf_logpdf_vjp_workspace_bytes")
-        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
-            self._vjp_ws = self._workspace(nbytes, t.device)
+        wt = self._weights(w, B, t.device, "w must have one entry per row of x")
+        ws = self._grad_ws("wf_logpdf_vjp_workspace_bytes", B, t.device)
         grad = self._new((self.n_params,))
-        _lib.check(L.wf_logpdf_vjp(self._h, self._p(t), B, self._p(wt), self._p(grad), self._p(self._vjp_ws), self._vjp_ws.numel(),
-                                   self._stream()), "wf_logpdf_vjp")
+        self._run("wf_logpdf_vjp", self._p(t), B, self._p(wt), self._p(grad), *ws)
         return grad
 
     def _jac_rows(self, x):
@@ -346,66 +356,47 @@ class DeviceModel:
         t, _ = self._to_dev(x)
         return t, self._new((t.shape[0], self.n_params))
 
-    def _jac_ws(self, nbytes, device):
-        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
-            self._vjp_ws = self._workspace(nbytes, device)
-        return self._vjp_ws
-
     def logpdf_jacobian(self, x, return_logp=False):
         """jac[b, p] = d log_pdf_b / d theta_p -> torch.cuda float32 [B, n_params] (jax.jacrev(log_pdf, argnums=0)(params, batch), vqmc.py:179, in
         flat leaf order: core.unflatten_batched gives the pytree); with return_logp also log_pdf [B] of the same sweep."""
-        L = _lib.lib()
         t, jac = self._jac_rows(x)
         B = t.shape[0]
-        ws = self._jac_ws(_lib.check(L.wf_logpdf_jac_workspace_bytes(self._h, B), "wf_logpdf_jac_workspace_bytes"), t.device)
+        ws = self._grad_ws("wf_logpdf_jac_workspace_bytes", B, t.device)
         lp = self._new((B,)) if return_logp else None
-        _lib.check(L.wf_logpdf_jac(self._h, self._p(t), B, self._p(jac), self._p(lp), self._p(ws), ws.numel(), self._stream()), "wf_logpdf_jac")
+        self._run("wf_logpdf_jac", self._p(t), B, self._p(jac), self._p(lp), *ws)
         return (jac, lp) if return_logp else jac
 
     def psi_jacobian(self, x, w_psi=None, w_lap=None):
         """jac[b, p] = w_psi[b] d psi_b / d theta_p + w_lap[b] d laplacian_b / d theta_p -> torch.cuda float32 [B, n_params]: the rows whose sum
         is psi_vjp.  Defaults w_psi = 1, w_lap = 0: jax.jacrev(psi, argnums=0)(params, batch)."""
         torch = _torch()
-        L = _lib.lib()
         t, jac = self._jac_rows(x)
         B = t.shape[0]
-        wp = torch.ones(B, dtype=torch.float32, device=t.device) if w_psi is None else torch.as_tensor(w_psi, dtype=torch.float32).to(t.device).contiguous()
-        wl = None if w_lap is None else torch.as_tensor(w_lap, dtype=torch.float32).to(t.device).contiguous()
-        if wp.numel() != B or (wl is not None and wl.numel() != B):
-            raise ValueError("w_psi / w_lap must have one entry per walker")
-        ws = self._jac_ws(_lib.check(L.wf_psi_jac_workspace_bytes(self._h, B), "wf_psi_jac_workspace_bytes"), t.device)
-        _lib.check(L.wf_psi_jac(self._h, self._p(t), B, self._p(wp), self._p(wl), self._p(jac), self._p(ws), ws.numel(), self._stream()), "wf_psi_jac")
+        message = "w_psi / w_lap must have one entry per walker"
+        wp = torch.ones(B, dtype=torch.float32, device=t.device) if w_psi is None else self._weights(w_psi, B, t.device, message)
+        wl = None if w_lap is None else self._weights(w_lap, B, t.device, message)
+        ws = self._grad_ws("wf_psi_jac_workspace_bytes", B, t.device)
+        self._run("wf_psi_jac", self._p(t), B, self._p(wp), self._p(wl), self._p(jac), *ws)
         return jac
 
     def logpdf_loss_grad(self, x, weight):
         """(log_pdf [B], weight * sum_b d log_pdf_b / d theta [n_params]) from one forward and one reverse sweep."""
-        L = _lib.lib()
         t, _ = self._to_dev(x)
         B = t.shape[0]
-        nbytes = _lib.check(L.wf_logpdf_vjp_workspace_bytes(self._h, B), "wf_logpdf_vjp_workspace_bytes")
-        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
-            self._vjp_ws = self._workspace(nbytes, t.device)
+        ws = self._grad_ws("wf_logpdf_vjp_workspace_bytes", B, t.device)
         lp, grad = self._new((B,)), self._new((self.n_params,))
-        _lib.check(L.wf_logpdf_loss_grad(self._h, self._p(t), B, float(weight), self._p(lp), self._p(grad), self._p(self._vjp_ws),
-                                         self._vjp_ws.numel(), self._stream()), "wf_logpdf_loss_grad")
+        self._run("wf_logpdf_loss_grad", self._p(t), B, float(weight), self._p(lp), self._p(grad), *ws)
         return lp, grad
 
     def vqmc_loss_grad(self, x, protons, running_average, global_count=None):
         """loss_fn_efficient and its gradient (vqmc.py:193-221) for the walkers x on this device, one fused pass.
         -> (sums fp64 [sum E_L, sum E_L^2, count] (torch.cuda), grad float32 [n_params] scaled by 1/global_count)."""
-        torch = _torch()
-        L = _lib.lib()
         t, _ = self._to_dev(x)
         B = t.shape[0]
-        pr = np.ascontiguousarray(np.asarray(protons, dtype=np.float32).reshape(-1))
-        nbytes = _lib.check(L.wf_psi_vjp_workspace_bytes(self._h, B), "wf_psi_vjp_workspace_bytes")
-        if self._vjp_ws is None or self._vjp_ws.numel() < nbytes:
-            self._vjp_ws = self._workspace(nbytes, t.device)
+        ws = self._grad_ws("wf_psi_vjp_workspace_bytes", B, t.device)
         el, grad = self._new((B,)), self._new((self.n_params,))
         inv = 1.0 / float(global_count if global_count else max(B, 1))
-        _lib.check(L.wf_vqmc_loss_grad(self._h, self._p(t), B, pr.ctypes.data if pr.size else None, pr.size, float(running_average), inv,
-                                       self._p(el), self._p(grad), self._p(self._vjp_ws), self._vjp_ws.numel(), self._stream()),
-                   "wf_vqmc_loss_grad")
+        self._run("wf_vqmc_loss_grad", self._p(t), B, *self._protons(protons), float(running_average), inv, self._p(el), self._p(grad), *ws)
         return self.block_sums(el), grad
 
     def adam_step(self, x, g, m, v, step, step_size, b1=0.9, b2=0.999, eps=1e-8):
@@ -413,8 +404,8 @@ class DeviceModel:
         for t in (x, g, m, v):
             if not t.is_cuda or not t.is_contiguous() or t.numel() != x.numel() or str(t.dtype) != "torch.float32":
                 raise ValueError("adam_step needs contiguous float32 cuda vectors of equal length")
-        _lib.check(_lib.lib().wf_adam_step(self._p(x), self._p(g), self._p(m), self._p(v), x.numel(), int(step), float(step_size), float(b1),
-                                           float(b2), float(eps), self._stream()), "wf_adam_step")
+        _lib.call("wf_adam_step", self._p(x), self._p(g), self._p(m), self._p(v), x.numel(), int(step), float(step_size), float(b1),
+                  float(b2), float(eps), self._stream())
 
     def make_train_state(self, x, m, v, first_step, ring_len=128, defer_eval_tables=False):
         """Device-side state of wf_vqmc_train_step around the Adam vectors x, m, v (float32 cuda, updated in place).
@@ -430,79 +421,59 @@ class DeviceModel:
                                   st["ring"].data_ptr(), int(ring_len), int(bool(defer_eval_tables)))
         return st
 
+    def train_step_workspace_bytes(self, batch):
+        """Workspace of train_step / train_step_local for `batch` walkers per step; WfError where the library has no fused step for them."""
+        return _lib.call("wf_vqmc_train_step_workspace_bytes", self._h, int(batch))
+
+    def mle_train_step_workspace_bytes(self, n):
+        """Workspace of mle_train_step for n resident rows."""
+        return _lib.call("wf_mle_train_step_workspace_bytes", self._h, int(n))
+
     def train_step(self, st, seed, batch, protons, step_size, b1=0.9, b2=0.999, eps=1e-8, exact_sampler=False):
         """One whole training step on the device (wf_vqmc_train_step): no host work, capturable in a hipGraph."""
-        L = _lib.lib()
-        pr = np.ascontiguousarray(np.asarray(protons, dtype=np.float32).reshape(-1))
-        nbytes = _lib.check(L.wf_vqmc_train_step_workspace_bytes(self._h, int(batch)), "wf_vqmc_train_step_workspace_bytes")
-        if st.get("ws") is None or st["ws"].numel() < nbytes:
-            st["ws"] = self._workspace(nbytes, st["x"].device)
-        _lib.check(L.wf_vqmc_train_step(self._h, ctypes.byref(st["c"]), int(seed), int(batch), pr.ctypes.data if pr.size else None, pr.size,
-                                        float(step_size), float(b1), float(b2), float(eps), int(bool(exact_sampler)), self._p(st["ws"]),
-                                        st["ws"].numel(), self._stream()), "wf_vqmc_train_step")
-        self._flat = None
-        self._dev_key = None
+        ws = self._train_ws(st, self.train_step_workspace_bytes(batch))
+        self._run("wf_vqmc_train_step", ctypes.byref(st["c"]), int(seed), int(batch), *self._protons(protons), float(step_size), float(b1),
+                  float(b2), float(eps), int(bool(exact_sampler)), *ws)
+        self._invalidate_host_copy()
 
     def train_step_local(self, st, seed, batch_local, protons, inv_global_batch, red, exact_sampler=False):
         """First half of a sharded training step (wf_vqmc_train_step_local): this rank's walkers -> red[n_params + 3] (float64 cuda)
         = [gradient contribution, sum E_L, sum E_L^2, local walkers]; the caller all-reduces red and calls train_step_apply."""
-        L = _lib.lib()
-        pr = np.ascontiguousarray(np.asarray(protons, dtype=np.float32).reshape(-1))
-        nbytes = _lib.check(L.wf_vqmc_train_step_workspace_bytes(self._h, int(batch_local)), "wf_vqmc_train_step_workspace_bytes")
-        if st.get("ws") is None or st["ws"].numel() < nbytes:
-            st["ws"] = self._workspace(nbytes, st["x"].device)
+        ws = self._train_ws(st, self.train_step_workspace_bytes(batch_local))
         if str(red.dtype) != "torch.float64" or red.numel() != self.n_params + 3 or not red.is_cuda or not red.is_contiguous():
             raise ValueError("red must be a contiguous float64 cuda vector of n_params + 3 entries")
-        _lib.check(L.wf_vqmc_train_step_local(self._h, ctypes.byref(st["c"]), int(seed), int(batch_local), pr.ctypes.data if pr.size else None,
-                                              pr.size, float(inv_global_batch), int(bool(exact_sampler)), self._p(red), self._p(st["ws"]),
-                                              st["ws"].numel(), self._stream()), "wf_vqmc_train_step_local")
+        self._run("wf_vqmc_train_step_local", ctypes.byref(st["c"]), int(seed), int(batch_local), *self._protons(protons), float(inv_global_batch),
+                  int(bool(exact_sampler)), self._p(red), *ws)
 
     def train_step_apply(self, st, red, step_size, b1=0.9, b2=0.999, eps=1e-8):
         """Second half (wf_vqmc_train_step_apply): Adam with the reduced gradient, image refill, loss ring, counter."""
-        _lib.check(_lib.lib().wf_vqmc_train_step_apply(self._h, ctypes.byref(st["c"]), self._p(red), float(step_size), float(b1), float(b2),
-                                                       float(eps), self._stream()), "wf_vqmc_train_step_apply")
-        self._flat = None
-        self._dev_key = None
+        self._run("wf_vqmc_train_step_apply", ctypes.byref(st["c"]), self._p(red), float(step_size), float(b1), float(b2), float(eps))
+        self._invalidate_host_copy()
 
     def mle_train_step(self, st, x, step_size, b1=0.9, b2=0.999, eps=1e-8):
         """One maximum-likelihood epoch on the device (wf_mle_train_step): no host work, capturable in a hipGraph."""
-        L = _lib.lib()
-        nbytes = _lib.check(L.wf_mle_train_step_workspace_bytes(self._h, int(x.shape[0])), "wf_mle_train_step_workspace_bytes")
-        if st.get("ws") is None or st["ws"].numel() < nbytes:
-            st["ws"] = self._workspace(nbytes, st["x"].device)
-        _lib.check(L.wf_mle_train_step(self._h, ctypes.byref(st["c"]), self._p(x), int(x.shape[0]), float(step_size), float(b1), float(b2),
-                                       float(eps), self._p(st["ws"]), st["ws"].numel(), self._stream()), "wf_mle_train_step")
-        self._flat = None
-        self._dev_key = None
-
-    @staticmethod
-    def _workspace(nbytes, device):
-        torch = _torch()
-        ws = torch.empty(int(nbytes), device=device, dtype=torch.uint8)
-        if os.environ.get("WF_POISON"):
-            ws.fill_(0xFF)   # NaN patterns: see dev_alloc_bytes in wf_runtime.cpp
-        return ws
+        n = int(x.shape[0])
+        ws = self._train_ws(st, self.mle_train_step_workspace_bytes(n))
+        self._run("wf_mle_train_step", ctypes.byref(st["c"]), self._p(x), n, float(step_size), float(b1), float(b2), float(eps), *ws)
+        self._invalidate_host_copy()
 
     def block_sums(self, v):
         """fp64 [sum v, sum v^2, count] on the device (deterministic order)."""
         torch = _torch()
-        L = _lib.lib()
         v = v.contiguous()
-        ws = torch.empty(int(L.wf_block_sums_workspace_bytes(v.numel())), device=v.device, dtype=torch.uint8)
+        ws = torch.empty(int(_lib.call("wf_block_sums_workspace_bytes", v.numel())), device=v.device, dtype=torch.uint8)
         out = torch.empty(3, device=v.device, dtype=torch.float64)
-        _lib.check(L.wf_block_sums(self._p(v), v.numel(), self._p(out), self._p(ws), ws.numel(), self._stream()), "wf_block_sums")
+        _lib.call("wf_block_sums", self._p(v), v.numel(), self._p(out), self._p(ws), ws.numel(), self._stream())
         return out
 
 
 def build_tables(kind, degree, n_internal_knots, n_mesh=2000):
     """Host-only: fp64 [4][n_bases][n_mesh] (+ (b_to_ob, ob_to_b) for kind == SPLINE_OB)."""
-    L = _lib.lib()
-    nb = _lib.check(L.wf_tables_build(kind, degree, n_internal_knots, n_mesh, None, None, None), "wf_tables_build")
+    nb = _lib.call("wf_tables_build", kind, degree, n_internal_knots, n_mesh, None, None, None)
     out = np.zeros((4, nb, n_mesh))
     if kind == _lib.SPLINE_OB:
         b2o, o2b = np.zeros((nb, nb)), np.zeros((nb, nb))
-        _lib.check(L.wf_tables_build(kind, degree, n_internal_knots, n_mesh, out.ctypes.data, b2o.ctypes.data, o2b.ctypes.data),
-                   "wf_tables_build")
+        _lib.call("wf_tables_build", kind, degree, n_internal_knots, n_mesh, out.ctypes.data, b2o.ctypes.data, o2b.ctypes.data)
         return out, b2o, o2b
-    _lib.check(L.wf_tables_build(kind, degree, n_internal_knots, n_mesh, out.ctypes.data, None, None), "wf_tables_build")
+    _lib.call("wf_tables_build", kind, degree, n_internal_knots, n_mesh, out.ctypes.data, None, None)
     return out

@@ -3,12 +3,11 @@
 The reference module is dead code (it calls the removed jax.ops API) and has no fixtures: parity is against the
 formulas as restated in oracle/wf_oracle.c.  Same argument names as the reference; tensors are torch.cuda or numpy.
 """
-import ctypes
-
 import numpy as np
 
 from .. import _lib
 
+P = _lib.ptr
 DEFAULT_MIN_BIN_WIDTH = DEFAULT_MIN_BIN_HEIGHT = DEFAULT_MIN_DERIVATIVE = 1e-3
 
 
@@ -25,10 +24,8 @@ def _call(inputs, uw, uh, ud, inverse, left, right, bottom, top, return_bin_idx)
         raise ValueError("shape mismatch between inputs and spline parameters")
     y, ld = torch.empty_like(x), torch.empty_like(x)
     b = torch.empty(shape, device=dev, dtype=torch.int32) if return_bin_idx else None
-    P = lambda a: ctypes.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(_lib.lib().wf_rqs_fwd(P(x), P(uw), P(uh), P(ud), N, K, ud.numel() // max(N, 1) if N else K - 1, int(bool(inverse)),
-                                     float(left), float(right), float(bottom), float(top), P(y), P(ld), P(b), stream), "wf_rqs_fwd")
+    _lib.call("wf_rqs_fwd", P(x), P(uw), P(uh), P(ud), N, K, ud.numel() // max(N, 1) if N else K - 1, int(bool(inverse)),
+              float(left), float(right), float(bottom), float(top), P(y), P(ld), P(b), _lib.stream_ptr())
     out = (y, ld, b) if return_bin_idx else (y, ld)
     return tuple(o.cpu().numpy() for o in out) if was_numpy else out
 
@@ -96,11 +93,8 @@ class NeuralSplineCoupling:
         K, tail, hidden = self.K, self.B, self.hidden
 
         def run(params, x, inverse):
-            import ctypes
             torch = __import__("torch")
-            from .. import _lib
             from ..core import flatten_params
-            L = _lib.lib()
             was_numpy = not hasattr(x, "detach")
             t = (torch.as_tensor(np.asarray(x, dtype=np.float32)) if was_numpy else x).to("cuda", dtype=torch.float32).contiguous()
             if t.dim() != 2 or t.shape[1] != dim:
@@ -109,10 +103,8 @@ class NeuralSplineCoupling:
             flat = torch.as_tensor(flatten_params(params)).to(t.device)
             y = torch.empty_like(t)
             ld = torch.empty(Bn, device=t.device, dtype=torch.float32)
-            ws = torch.empty(int(_lib.check(L.wf_nsc_workspace_bytes(Bn, dim, K), "wf_nsc_workspace_bytes")), device=t.device, dtype=torch.uint8)
-            P = lambda a: ctypes.c_void_p(a.data_ptr())
-            _lib.check(L.wf_nsc_fwd(P(t), Bn, dim, K, tail, hidden, P(flat), int(inverse), P(y), P(ld), P(ws), ws.numel(),
-                                    ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)), "wf_nsc_fwd")
+            ws = torch.empty(int(_lib.call("wf_nsc_workspace_bytes", Bn, dim, K)), device=t.device, dtype=torch.uint8)
+            _lib.call("wf_nsc_fwd", P(t), Bn, dim, K, tail, hidden, P(flat), int(inverse), P(y), P(ld), P(ws), ws.numel(), _lib.stream_ptr(t.device))
             return (y.cpu().numpy(), ld.cpu().numpy()) if was_numpy else (y, ld)
 
         def direct_fun(params, x, **kw):

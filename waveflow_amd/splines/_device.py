@@ -11,6 +11,7 @@ from ..utils import table_cache
 
 NAMES = {_lib.SPLINE_I: "I", _lib.SPLINE_M: "M", _lib.SPLINE_B: "B"}
 MAX_BASES = 64
+P = _lib.ptr
 
 
 def make_knots(kind, k, n_internal_knots):
@@ -93,7 +94,7 @@ class DeviceSpline:
             dev = torch.cuda.current_device() if torch.cuda.is_available() else 0
             h = ctypes.c_void_p()
             aux = self.aux.ctypes.data if self.aux is not None else None
-            _lib.check(self._L.wf_spline_create(ctypes.byref(self.desc), self.tables.ctypes.data, aux, dev, ctypes.byref(h)), "wf_spline_create")
+            _lib.call("wf_spline_create", ctypes.byref(self.desc), self.tables.ctypes.data, aux, dev, ctypes.byref(h))
             self._h, self._dev = h, dev
         return self._h
 
@@ -109,8 +110,7 @@ class DeviceSpline:
         return t.to(device=f"cuda:{self._dev}", dtype=torch.float32).contiguous()
 
     def _stream(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+        return _lib.stream_ptr(self._dev)
 
     def _rows(self, params, width):
         h = self.handle()
@@ -128,8 +128,7 @@ class DeviceSpline:
             raise ValueError("params and x must have the same number of rows")
         y = torch.empty(c.shape[0], device=c.device, dtype=torch.float32)
         dy = torch.empty_like(y) if grad else None
-        _lib.check(self._L.wf_spline_apply(h, c.data_ptr(), c.shape[0], xt.data_ptr(), nd, y.data_ptr(), dy.data_ptr() if grad else None,
-                                           self._stream()), "wf_spline_apply")
+        _lib.call("wf_spline_apply", h, P(c), c.shape[0], P(xt), nd, P(y), P(dy), self._stream())
         return (y, dy) if grad else y
 
     def reverse(self, params, y, tol):
@@ -139,8 +138,7 @@ class DeviceSpline:
         if yt.numel() != c.shape[0]:
             raise ValueError("params and y must have the same number of rows")
         x = torch.empty(c.shape[0], device=c.device, dtype=torch.float32)
-        _lib.check(self._L.wf_spline_reverse(h, c.data_ptr(), c.shape[0], yt.data_ptr(), float(tol), x.data_ptr(), self._stream()),
-                   "wf_spline_reverse")
+        _lib.call("wf_spline_reverse", h, P(c), c.shape[0], P(yt), float(tol), P(x), self._stream())
         return x
 
     def rowwise(self, fn, weights):
@@ -150,15 +148,14 @@ class DeviceSpline:
         if w.dim() != 2:
             raise ValueError("weights must be [N, nw]")
         out = torch.empty_like(w)
-        _lib.check(getattr(self._L, fn)(h, w.data_ptr(), w.shape[0], w.shape[1], out.data_ptr(), self._stream()), fn)
+        _lib.call(fn, h, P(w), w.shape[0], w.shape[1], P(out), self._stream())
         return out
 
     def sample(self, rng, params, num_samples, max_proposals):
         import torch
         h, c = self._rows(params, self.nc)
         x = torch.empty((c.shape[0], int(num_samples)), device=c.device, dtype=torch.float32)
-        _lib.check(self._L.wf_spline_sample(h, seed_from(rng), c.data_ptr(), c.shape[0], int(num_samples), int(max_proposals), x.data_ptr(),
-                                            self._stream()), "wf_spline_sample")
+        _lib.call("wf_spline_sample", h, seed_from(rng), P(c), c.shape[0], int(num_samples), int(max_proposals), P(x), self._stream())
         bad = torch.isnan(x).any(dim=1).nonzero()
         if bad.numel():
             raise RuntimeError(f"sample_fun_vec: row {int(bad[0, 0])} exhausted {max_proposals} proposals for a slot (acceptance rate too "

@@ -7,8 +7,6 @@ def get_num_inversion_count(coordinates):
     A cuda tensor is counted on the device (wf_inversion_count) and returned as an int32 cuda tensor; anything else on the host,
     one vectorised comparison of all pairs (the reference's per-row insertion loop, coordinates.py:17-51, counts the same pairs)."""
     if hasattr(coordinates, "is_cuda") and coordinates.is_cuda:
-        import ctypes
-
         import torch
 
         from .. import _lib
@@ -16,8 +14,7 @@ def get_num_inversion_count(coordinates):
         B, D = x.shape
         out = torch.empty(B, dtype=torch.int32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().wf_inversion_count(ctypes.c_void_p(x.data_ptr()) if B else None, B, D, ctypes.c_void_p(out.data_ptr()) if B else None,
-                                                     ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "wf_inversion_count")
+            _lib.call("wf_inversion_count", _lib.ptr(x), B, D, _lib.ptr(out), _lib.stream_ptr(x.device))
         return out
     c = np.asarray(coordinates)
     i, j = np.triu_indices(c.shape[1], k=1)

@@ -23,7 +23,7 @@ def cache_file_names(kind, degree, n_internal_knots, n_mesh=2000):
     """-> dict of the file names (no directory) the reference looks for: {"nd": [4 names]} for I / M; for B also "ob", "b_to_ob", "ob_to_b"."""
     if kind not in _KINDS:
         raise ValueError("kind must be 'I', 'M' or 'B'")
-    nb = _lib.check(_lib.lib().wf_tables_build(_KINDS[kind], degree, n_internal_knots, n_mesh, None, None, None), "wf_tables_build")
+    nb = _lib.call("wf_tables_build", _KINDS[kind], degree, n_internal_knots, n_mesh, None, None, None)
     if kind == "B":
         stem = f"degree_{degree}_niknots_{nb + 1}_nmp_{n_mesh}"
         return {"nd": [f"b_{stem}_nd_{nd}.npy" for nd in range(4)], "ob": [f"ob_{stem}_nd_{nd}.npy" for nd in range(4)],

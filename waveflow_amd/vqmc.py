@@ -89,6 +89,14 @@ def create_train_state(box_length, learning_rate, n_particle, rng=0, xu_coord_ty
     return psi, log_pdf, sample, opt_init(params), opt_update, get_params
 
 
+def _protons_of(h_fn):
+    """The proton positions a Hamiltonian closure of physics.construct_hamiltonian_function carries."""
+    pos = getattr(h_fn, "protons", None)
+    if pos is None:
+        raise TypeError("h_fn must come from waveflow_amd.utils.physics.construct_hamiltonian_function")
+    return pos
+
+
 def loss_fn_efficient(params, psi, h_fn, batch, running_average):
     """vqmc.py:193-200 (value only): mean of H psi / (psi + 1e-8) over the batch."""
     p = helpers._np(psi(params, batch)).reshape(-1, 1)
@@ -103,9 +111,7 @@ def loss_and_grad_efficient(params, psi, h_fn, batch, running_average, group=Non
     from .distributed import all_reduce_gradient_and_moments, global_count, moments_to_stats
     model = psi.model
     model.ensure_params(params)
-    pos = getattr(h_fn, "protons", None)
-    if pos is None:
-        raise TypeError("h_fn must come from waveflow_amd.utils.physics.construct_hamiltonian_function")
+    pos = _protons_of(h_fn)
     # the tangent rule's 1 / batch factor is applied on the device, so the global count is needed up front
     # `group=None` means NOT distributed in every function of this module (as in ModelTrainer): no collective is entered, whatever
     # process group happens to be initialised -- a rank that passes None must not wait in an all-reduce its peers never reach.
@@ -128,9 +134,7 @@ def _energy_terms(params, psi, h_fn, batch):
     """One forward sweep: (model, x on the device, H psi, psi, laplacian) as float32 cuda vectors."""
     model = psi.model
     model.ensure_params(params)
-    pos = getattr(h_fn, "protons", None)
-    if pos is None:
-        raise TypeError("h_fn must come from waveflow_amd.utils.physics.construct_hamiltonian_function")
+    pos = _protons_of(h_fn)
     x, _ = model._to_dev(batch)
     hpsi, ps, lap = model.hamiltonian(x, pos, return_psi=True, return_laplacian=True)
     return model, x, hpsi, ps, lap
@@ -347,8 +351,11 @@ class ModelTrainer:
         # Sharded over several processes: the same sequence in two halves around the step's one all-reduce.
         fused = self.use_graph and local_batch >= 1
         if fused:
-            from . import _lib
-            fused = _lib.lib().wf_vqmc_train_step_workspace_bytes(psi.model._h, int(local_batch)) > 0
+            from ._lib import WfError
+            try:
+                fused = psi.model.train_step_workspace_bytes(local_batch) > 0
+            except WfError:   # (the library has no fused step for this model or batch)
+                fused = False
         if fused:
             params, loss, energies = self._train_graphed(psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict,
                                                          save_dir, rng, verbose, group=group if distributed else None, rank=rank,
@@ -383,7 +390,6 @@ class ModelTrainer:
         wf_vqmc_train_step_apply, issued call by call (WF_GRAPH_COLLECTIVE=1 captures it with the RCCL collective inside) -- either
         way without a host synchronisation per step."""
         import torch
-        from . import _lib
         from .distributed import _all_reduce_sum
         model = psi.model
         # (the steps leave out the tables only the large-batch evaluation kernel reads; every evaluation below goes through
@@ -401,7 +407,7 @@ class ModelTrainer:
         if group is None:
             def step():
                 model.train_step(st, seed, self.batch_size, h_fn.protons, self.learning_rate, exact_sampler=self.exact_sampler)
-            nbytes = _lib.check(_lib.lib().wf_vqmc_train_step_workspace_bytes(model._h, self.batch_size), "wf_vqmc_train_step_workspace_bytes")
+            nbytes = model.train_step_workspace_bytes(self.batch_size)
             capture = True
         else:
             import torch.distributed as dist
@@ -412,7 +418,7 @@ class ModelTrainer:
                                        exact_sampler=self.exact_sampler)
                 _all_reduce_sum(red, group)
                 model.train_step_apply(st, red, self.learning_rate)
-            nbytes = _lib.check(_lib.lib().wf_vqmc_train_step_workspace_bytes(model._h, int(local_batch)), "wf_vqmc_train_step_workspace_bytes")
+            nbytes = model.train_step_workspace_bytes(local_batch)
             # Capturing the collective in the graph measured no faster than issuing the three calls (4.91 vs 4.94 s per 20 000 steps, one
             # rank) and could not be tried on several GPUs here: opt-in.
             capture = dist.get_backend(group) == "nccl" and os.environ.get("WF_GRAPH_COLLECTIVE") == "1"
