@@ -13,7 +13,8 @@ SOURCES = ["wf_tables.cpp", "wf_runtime.cpp", "wf_model_build.cpp", "wf_model_im
            "wf_scalar_inst_d78.hip", "wf_scalar_inst_n64.hip", "wf_scalar_inst_n64_d56.hip",
            "wf_scalar_inst_n64_d78.hip", "wf_kernels_mfma.hip", "wf_mfma_inst_d2.hip", "wf_mfma_inst_d2t2.hip", "wf_mfma_inst_d34.hip",
            "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip",
-           "wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_sample.hip", "wf_kernels_etile_dir.hip", "wf_kernels_spline.hip"]
+           "wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_sample.hip", "wf_kernels_etile_dir.hip", "wf_kernels_spline.hip",
+           "wf_kernels_sr.hip"]
 # -ffp-contract=off: the index arithmetic and the table lerp keep the reference's separate
 # multiply / add roundings; dot products that may fuse say so with explicit fmaf / MFMA.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
@@ -28,6 +29,8 @@ FLAGS += os.environ.get("WF_CXXFLAGS", "").split()  # extra compiler flags (e.g.
 # v_pk_add_f32 in the D >= 3 builds): the target feature is switched off for these units (the host pass does not know the feature and says
 # so on stderr; harmless), and isa_guard.check() disassembles the linked library and refuses it if one is left.
 MFMA_FLAGS = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# units that issue MFMA under a file name that says neither "mfma" nor "etile" (the fp64 products of stochastic reconfiguration)
+MFMA_UNITS = {"wf_kernels_sr.hip"}
 # per translation unit: the two-row-block reverse kernels under the max-ilp scheduling strategy (-6 % for them, +1 % for the one-row-block form)
 EXTRA_FLAGS = {"wf_etile_bwd_k2.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
@@ -77,7 +80,7 @@ def _library_current():
     except OSError:
         return False
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
-    deps.append(os.path.join(HERE, "..", "include", "waveflow_hip.h"))
+    deps += [os.path.join(HERE, "..", "include", h) for h in ("waveflow_hip.h", "waveflow_sr.h")]
     return all(os.path.getmtime(d) <= t for d in deps if os.path.exists(d))
 
 
@@ -94,7 +97,7 @@ def build(force=False, verbose=False):
     for s in srcs:
         o = os.path.join(OBJ, s + ".o")
         if force or _stale(o):
-            cmd = [_hipcc()] + FLAGS + (MFMA_FLAGS if ("mfma" in s or "etile" in s) else []) + EXTRA_FLAGS.get(s, []) + (["-x", "hip"] if s.endswith(".cpp") else [])
+            cmd = [_hipcc()] + FLAGS + (MFMA_FLAGS if ("mfma" in s or "etile" in s or s in MFMA_UNITS) else []) + EXTRA_FLAGS.get(s, []) + (["-x", "hip"] if s.endswith(".cpp") else [])
             cmd += ["-MD", "-MF", o + ".d", "-c", os.path.join(CSRC, s), "-o", o]
             jobs.append(cmd)
 

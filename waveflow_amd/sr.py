@@ -1,0 +1,182 @@
+"""Stochastic reconfiguration (the natural gradient of variational Monte Carlo) from per-walker Jacobian rows, in its B x B ("minSR") form:
+the ctypes surface of include/waveflow_sr.h.
+
+With O[b][k] = d ln psi_b / d theta_k, local energies e, H = I - 1 1^T / B and lambda > 0,
+    d = (O^T H O / B + lambda I)^-1 (2 / B) O^T H e  =  (2 / B) O^T H y,    (H O O^T H / B + lambda I) y = H e
+-- `gram`, `solve`, `apply`, and `natural_gradient` for the three in a row.  The rows are read twice and never rewritten; lambda is
+`damping + relative_damping * trace(Tbar) / B`.  Everything runs on the GPU that holds the rows, on torch's current stream; there is no
+CPU fallback, and arguments are checked before anything is launched (ValueError).
+"""
+import ctypes
+
+from . import _lib
+
+MAX_WALKERS = 4096   # wf_sr_solve: Tbar is 128 MiB there
+
+_vp, _i32, _i64, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+_ws = [_vp, _i64]    # (workspace_dev, workspace_bytes)
+# name -> (restype, argtypes): every function of include/waveflow_sr.h, in its order (tests/test_sr_host.py holds the two against each other)
+PROTOTYPES = {
+    "wf_sr_workspace_bytes": (_i64, [_i64, _i64]),
+    "wf_sr_gram": (_i32, [_vp, _i64, _i64, _i64, _vp] + _ws + [_vp]),
+    "wf_sr_solve": (_i32, [_vp, _i64, _vp, _f64, _f64, _vp, _vp] + _ws + [_vp]),
+    "wf_sr_apply": (_i32, [_vp, _i64, _i64, _i64, _vp, _f64, _vp] + _ws + [_vp]),
+}
+
+_bound = None
+
+
+class NotPositiveDefinite(ArithmeticError):
+    """The Cholesky factorisation of Tbar + lambda I met a pivot that is not positive; `pivot` is its 1-based index."""
+
+    def __init__(self, pivot):
+        self.pivot = int(pivot)
+        super().__init__(f"stochastic reconfiguration: pivot {self.pivot} of the shifted B x B matrix is not positive (more damping, or non-finite rows)")
+
+
+def lib():
+    """The handle of _lib.lib() with PROTOTYPES applied to it."""
+    global _bound
+    L = _lib.lib()
+    if _bound is not L:
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            f = getattr(L, name)
+            f.restype = restype
+            f.argtypes = argtypes
+        _bound = L
+    return L
+
+
+# ---- checks: all of them before the first launch, none needs a GPU
+
+def _check_damping(damping, relative_damping):
+    damping, relative_damping = float(damping), float(relative_damping)
+    if not damping >= 0.0 or not relative_damping >= 0.0:
+        raise ValueError(f"damping and relative_damping must be >= 0, got {damping} and {relative_damping}")
+    if damping == 0.0 and relative_damping == 0.0:
+        raise ValueError("damping and relative_damping are both zero: the centred B x B matrix is singular without a shift")
+    return damping, relative_damping
+
+
+def _check_rows(rows, limit=None):
+    """-> (B, P, ld).  float32 cuda [B, P] whose rows are contiguous (a column slice of a wider contiguous matrix is fine: ld is its row stride)."""
+    import torch
+    if not hasattr(rows, "is_cuda") or rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("rows must be a non-empty 2-d torch tensor [B, P]")
+    if rows.dtype != torch.float32:
+        raise ValueError(f"rows must be float32, got {rows.dtype}")
+    B, P = int(rows.shape[0]), int(rows.shape[1])
+    ld = int(rows.stride(0)) if B > 1 else max(int(rows.stride(0)), P)
+    if (P > 1 and rows.stride(1) != 1) or ld < P:
+        raise ValueError("rows must be contiguous along the parameter axis (stride 1, row stride >= P)")
+    if limit is not None and B > limit:
+        raise ValueError(f"{B} walkers: the B x B solve is built for at most {limit}")
+    if not rows.is_cuda:
+        raise ValueError("rows must be a cuda tensor: stochastic reconfiguration has no CPU fallback")
+    return B, P, ld
+
+
+def _check_vector(v, n, dtype, what, device):
+    import torch
+    if not hasattr(v, "is_cuda") or v.dim() != 1 or v.numel() != n:
+        raise ValueError(f"{what} must be a vector of {n} entries")
+    if not v.is_cuda or v.device != device:
+        raise ValueError(f"{what} must be a cuda tensor on the device of the other operands (no CPU fallback)")
+    if dtype is not None and v.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}, got {v.dtype}")
+    if dtype is None and not torch.is_floating_point(v):
+        raise ValueError(f"{what} must be floating point")
+
+
+def _check_matrix(T):
+    import torch
+    if not hasattr(T, "is_cuda") or T.dim() != 2 or T.shape[0] != T.shape[1] or T.shape[0] < 1:
+        raise ValueError("T must be a square 2-d torch tensor")
+    if T.dtype != torch.float64 or not T.is_contiguous():
+        raise ValueError("T must be contiguous float64")
+    if not T.is_cuda:
+        raise ValueError("T must be a cuda tensor: stochastic reconfiguration has no CPU fallback")
+    if T.shape[0] > MAX_WALKERS:
+        raise ValueError(f"{T.shape[0]} walkers: the B x B solve is built for at most {MAX_WALKERS}")
+    return int(T.shape[0])
+
+
+# ---- launches
+
+def _workspace(B, P, device):
+    from .core import DeviceModel
+    nbytes = _lib.check(lib().wf_sr_workspace_bytes(B, P), "wf_sr_workspace_bytes")
+    return DeviceModel._workspace(nbytes, device)   # (poisoned under WF_POISON like every workspace)
+
+
+def _gram(rows, B, P, ld, ws):
+    import torch
+    T = torch.empty((B, B), dtype=torch.float64, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(lib().wf_sr_gram(rows.data_ptr(), B, P, ld, T.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(rows.device)), "wf_sr_gram")
+    return T
+
+
+def _solve(T, B, rhs, damping, relative_damping, ws):
+    import torch
+    y = torch.empty(B, dtype=torch.float64, device=T.device)
+    info = torch.empty(1, dtype=torch.int32, device=T.device)
+    with torch.cuda.device(T.device):
+        _lib.check(lib().wf_sr_solve(T.data_ptr(), B, rhs.data_ptr(), damping, relative_damping, y.data_ptr(), info.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _lib.stream_ptr(T.device)), "wf_sr_solve")
+    return y, info
+
+
+def _apply(rows, B, P, ld, y, scale, ws):
+    import torch
+    out = torch.empty(P, dtype=torch.float32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(lib().wf_sr_apply(rows.data_ptr(), B, P, ld, y.data_ptr(), float(scale), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _lib.stream_ptr(rows.device)), "wf_sr_apply")
+    return out
+
+
+# ---- surface
+
+def gram(rows, workspace=None):
+    """Tbar = H (rows rows^T) H / B -> float64 cuda [B, B], exactly symmetric (wf_sr_gram)."""
+    B, P, ld = _check_rows(rows)
+    return _gram(rows, B, P, ld, workspace if workspace is not None else _workspace(B, P, rows.device))
+
+
+def solve(T, rhs, damping=0.0, relative_damping=1e-3, workspace=None):
+    """(T + lambda I) y = rhs with lambda = damping + relative_damping * trace(T) / B -> (y float64 [B], info int32 cuda [1]).  T (float64 cuda
+    [B, B]) is overwritten: its lower triangle holds the Cholesky factor afterwards.  info is 0, or the 1-based index of the first pivot that
+    is not positive (y is NaN then); nothing here waits for the device, reading `info` does (wf_sr_solve)."""
+    damping, relative_damping = _check_damping(damping, relative_damping)
+    B = _check_matrix(T)
+    import torch
+    _check_vector(rhs, B, torch.float64, "rhs", T.device)
+    return _solve(T, B, rhs.contiguous(), damping, relative_damping, workspace if workspace is not None else _workspace(B, 1, T.device))
+
+
+def apply(rows, y, scale, workspace=None):
+    """out[p] = scale * sum_b (y_b - mean y) rows[b][p] -> float32 cuda [P] (wf_sr_apply)."""
+    import torch
+    B, P, ld = _check_rows(rows)
+    _check_vector(y, B, torch.float64, "y", rows.device)
+    return _apply(rows, B, P, ld, y.contiguous(), scale, workspace if workspace is not None else _workspace(B, P, rows.device))
+
+
+def natural_gradient(rows, e_loc, damping=0.0, relative_damping=1e-3):
+    """d = (S + lambda I)^-1 g for rows O = d ln psi / d theta [B, P] and local energies e_loc [B]: S = O^T H O / B, g = (2 / B) O^T H e,
+    lambda = damping + relative_damping * trace(Tbar) / B -> float32 cuda [P].  Three library calls on the current stream, then one read of the
+    solver's status: NotPositiveDefinite if a pivot was not positive."""
+    import torch
+    damping, relative_damping = _check_damping(damping, relative_damping)
+    B, P, ld = _check_rows(rows, limit=MAX_WALKERS)
+    _check_vector(e_loc, B, None, "e_loc", rows.device)
+    ws = _workspace(B, P, rows.device)
+    T = _gram(rows, B, P, ld, ws)
+    e = e_loc.double()
+    y, info = _solve(T, B, e - e.mean(), damping, relative_damping, ws)
+    d = _apply(rows, B, P, ld, y, 2.0 / B, ws)
+    pivot = int(info.item())
+    if pivot != 0:
+        raise NotPositiveDefinite(pivot)
+    return d

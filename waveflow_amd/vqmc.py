@@ -251,6 +251,35 @@ def log_psi_jacobian(psi):
     return jac
 
 
+def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=1e-3, group=None):
+    """Stochastic reconfiguration on the walkers of `batch`: d = (S + lambda I)^-1 g with O_k(x_b) = d ln psi_b / d theta_k (the rows of
+    log_psi_jacobian, written once with the weight 1 / (psi + 1e-8)), S = O^T H O / B, g = (2 / B) O^T H e_loc, e_loc = H psi / (psi + 1e-8)
+    and lambda = damping + relative_damping * trace(H O O^T H / B) / B, solved in its B x B form (waveflow_amd.sr).
+    -> (d float32 cuda [n_params], loss = mean e_loc).  Sharded walkers (`group`) are not supported."""
+    from . import sr
+    if group is not None:
+        raise NotImplementedError("stochastic reconfiguration over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
+    sr._check_damping(damping, relative_damping)
+    model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
+    inv = 1.0 / (ps + 1e-8)
+    e_loc = hpsi * inv
+    rows = model.psi_jacobian(x, w_psi=inv)
+    d = sr.natural_gradient(rows, e_loc, damping=damping, relative_damping=relative_damping)
+    return d, float(e_loc.double().mean())
+
+
+def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **damping):
+    """One stochastic-reconfiguration step theta <- theta - lr d (sr_natural_gradient; `damping`: its damping / relative_damping;
+    learning_rate: a number, or a schedule called with `epoch`) -> (new params, loss).  `params` is left as it is: the result is a new
+    pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one."""
+    d, loss_val = sr_natural_gradient(params, psi, h_fn, batch, group=group, **damping)
+    lr = float(learning_rate(epoch) if callable(learning_rate) else learning_rate)
+    if isinstance(params, DeviceParams):
+        return DeviceParams(params.template, params.flat - lr * d.to(params.flat.device), params.version + 1), loss_val
+    flat = flatten_params(params).astype(np.float32)
+    return checkpoint.unflatten_like(params, flat - np.float32(lr) * d.cpu().numpy()), loss_val
+
+
 def _save_optimizer_state(save_dir, opt_state, epoch):
     """Adam's moments next to the reference's artefacts (the reference checkpoints parameters only, vqmc.py:96-100, and a restart
     there begins with a fresh optimiser): `optimizer_state.npz` {m, v, epoch}, rewritten at every checkpoint."""
@@ -301,13 +330,20 @@ class ModelTrainer:
         self.use_graph = True  # single process: capture the whole step (wf_vqmc_train_step) in a hipGraph and replay it
         self.seed = 2          # vqmc.py:57: PRNGKey(2)
         self.exact_sampler = False   # False: the reference's sampler (made.py:88 quirk); True: draws from |psi|^2
+        self.optimizer = 'adam'      # 'sr': stochastic reconfiguration steps (train_step_sr), eager, one process
+        self.sr_damping = {}         # damping / relative_damping of train_step_sr (its defaults when empty)
 
     def start_training(self, restart=False, verbose=True, group=None):
         """Under torch.distributed (one process per GPU, `torchrun examples/run_vqmc.py`) the walkers of a step are split over
         the ranks: every rank builds the same model from the same seed, draws batch_size / world walkers with its own sampler
         stream, and the step's single all-reduce (gradient + energy moments) keeps the replicas identical; rank 0 writes."""
         import torch.distributed as dist
+        optimizer = getattr(self, "optimizer", "adam")
+        if optimizer not in ('adam', 'sr'):
+            raise ValueError(f"optimizer must be 'adam' or 'sr', got {optimizer!r}")
         distributed = dist.is_available() and dist.is_initialized()
+        if optimizer == 'sr' and (distributed or group is not None):
+            raise NotImplementedError("optimizer='sr' runs in one process: stochastic reconfiguration over sharded walkers is not implemented")
         if distributed and group is None:
             group = dist.group.WORLD   # (None would read as "not distributed" further down: the default group, explicitly)
         rank = dist.get_rank(group) if distributed else 0
@@ -349,6 +385,11 @@ class ModelTrainer:
         # the whole step as one captured launch sequence, where the library has it (models the sweeps cover; the wave sampler: <= 131072 walkers
         # per step, no such limit where the staged large-batch sampler applies); otherwise the host-stepped loop below (sampler, loss + gradient, Adam: three library calls per step)
         # Sharded over several processes: the same sequence in two halves around the step's one all-reduce.
+        if optimizer == 'sr':
+            params = self._train_sr(psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose)
+            self.params, self.loss, self.energies = params, loss, energies
+            self.psi, self.log_pdf, self.sample, self.h_fn = psi, log_pdf, sample, h_fn
+            return params, loss
         fused = self.use_graph and local_batch >= 1
         if fused:
             from ._lib import WfError
@@ -381,6 +422,25 @@ class ModelTrainer:
         self.params, self.loss, self.energies = params, loss, energies
         self.psi, self.log_pdf, self.sample, self.h_fn = psi, log_pdf, sample, h_fn
         return params, loss
+
+    def _train_sr(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose):
+        """The host-stepped loop of start_training with train_step_sr in the place of the Adam step: eager (the solver's status is read every
+        step), parameters on the device in opt_state.x, no optimiser state to save.  `loss` and `energies` grow in place."""
+        params = get_params(opt_state)
+        for epoch in range(start_epoch + 1, start_epoch + self.num_epochs + 1):
+            ckpt_seed, step_seed = int(rng.integers(1 << 31)), int(rng.integers(1 << 31))
+            if epoch % self.log_every == 0 or epoch == 1:
+                helpers.create_checkpoint_wavefunc(ckpt_seed, save_dir, psi, sample, params, epoch, loss, energies, system_dict)
+            batch = sample(step_seed, params, self.batch_size, exact_inverse=self.exact_sampler)
+            new_params, new_loss = train_step_sr(epoch, psi, h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}))
+            opt_state.x.copy_(new_params.flat)
+            opt_state.version += 1
+            params = get_params(opt_state)
+            if epoch % self.log_every == 0 and verbose:
+                print(f"epoch {epoch} | Loss: {round(float(new_loss), 3)}")
+            loss.append(new_loss)
+            energies.append([new_loss])
+        return params
 
     def _train_graphed(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose,
                        group=None, rank=0, local_batch=None):
