@@ -99,7 +99,9 @@ typedef struct {
     float normal_offset;        /* Normal(offset) */
     int32_t n_constrained_left; /* constrained_dimension_indices_left, model_factory.py:124-129 */
     int32_t constrained_left[WF_MAX_DIM];
-    int32_t n_mesh;             /* n_spline_base_mesh_points (2000) */
+    int32_t n_mesh;             /* n_spline_base_mesh_points (2000), one size for the layers' and the prior's tables; >= 2, and >= the basis count of
+                                 * an orthogonalised (Waveflow) prior -- fewer points are WF_ERR_NUMERIC.  Tested on every path at 33 .. 4001 points
+                                 * with spline degrees 1 .. 8 (tests/test_gpu_degrees_and_meshes.py) */
     float i_reverse_tol;        /* IMADE reverse_fun_tol (bisection tolerance of the inverse, isplines_jax.py:153-156) */
     /* set_nn_output_grad_to_zero of the layers' / the prior's conditioner (model_factory.py:55-67, ABI 2):
      *   bij[d][j] = g_d(x) * head(o[d][j]) + z[d][j],   g_0 = 1, g_d = prod_{i<d} x_i^3  (x: the conditioner's input),

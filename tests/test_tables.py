@@ -59,3 +59,15 @@ def test_table_errors():
     assert nb == 19
     out = np.zeros((4, nb, 2000))
     assert L.wf_tables_build(_lib.SPLINE_OB, 5, 15, 2000, out.ctypes.data, None, None) == -6
+
+
+def test_ortho_tables_on_fewer_mesh_points_than_bases_are_refused():
+    """28 B-spline bases (k = 6, 23 internal knots) sampled on fewer than 28 mesh points have a singular Gram matrix: WF_ERR_NUMERIC with a message,
+    not tables built from rounding residue (27 points gave entries of 4e17).  As many points as bases still build."""
+    import pytest
+    for n_mesh in (17, 27):
+        with pytest.raises(_lib.WfError) as e:
+            build_tables(_lib.SPLINE_OB, 6, 23, n_mesh)
+        assert e.value.status == -6 and "table" in str(e.value), (n_mesh, str(e.value))
+    OB, b2o, o2b = build_tables(_lib.SPLINE_OB, 6, 23, 28)
+    assert OB.shape == (4, 28, 28) and np.isfinite(OB).all()

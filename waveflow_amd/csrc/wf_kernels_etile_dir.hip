@@ -53,7 +53,8 @@ __global__ void k_edir_box(const float* __restrict__ xg, int64_t B, float L, flo
     J sum = jc(0.0f);
 #pragma unroll
     for (int d = 0; d < D; ++d) sum = sum + x[d];
-    const J mean = sum * (1.0f / (float)D);
+    J mean = sum * (1.0f / (float)D);
+    if constexpr ((D & (D - 1)) != 0) mean.v = sum.v / (float)D;   // (the value by the reference's division: wf_kernels_wave.hip, box_forward)
     const J l = mean - x[0], wd = x[D - 1] - x[0];
     J ld = jc(0.0f), space = jc(2 * L);
 #pragma unroll

@@ -330,7 +330,10 @@ __device__ __forceinline__ void box_forward(const ModelDev& md, T (&cur)[D], T& 
         T sm = cst<T>(0.0f);
 #pragma unroll
         for (int d = 0; d < D; ++d) sm = sm + cur[d];
-        const T mean = sm * (1.0f / (float)D);
+        T mean = sm * (1.0f / (float)D);
+        // the value by the reference's division (made.py:160: jnp.mean; the scalar and the matrix-core kernel divide too): 1 / D is inexact for D = 3, 5, 6, 7,
+        // and (mean + L) - l below cancels most of the mean next to the box's corner -- one ulp of the mean was 7e-6 of the last flow coordinate there
+        if constexpr ((D & (D - 1)) != 0) mean.c0 = sm.c0 / (float)D;
         const T l = mean - cur[0];
         const T wd = cur[D - 1] - cur[0];
         T space = cst<T>(2 * L);
@@ -1005,16 +1008,26 @@ __device__ __forceinline__ float lerp0(const float* __restrict__ tab, const Lerp
 // LDS copy of every 32nd row of the order-0 I-spline table (the first round of the mesh search): 64 rows, padded so that the lanes' 16-byte reads of
 // their own rows spread over the banks.  The sampler is bound by L2 bandwidth on these rows (PMC: 1 350 L2 requests per walker, 10.7 TB/s).
 template <int NBK> constexpr int kCoarseStride = 32 * NBK + 4;
-template <int NBK>
+// Mesh points between two lanes of the first round.  64 lanes x 32 points reach 2048 mesh points: the kernels of such meshes are built with the
+// constant (BIG = false).  Beyond them (BIG, chosen by launch_wave_sample) it is the multiple of 32 with which 64 lanes still reach the last point:
+// 64 for 2049 .. 4096 points.
+constexpr int kCoarseMeshMax = 64 * 32;
+template <bool BIG>
+__device__ __forceinline__ int coarse_step(int n_mesh) {
+    if constexpr (BIG) return max(32, ((n_mesh + 63) / 64 + 31) / 32 * 32);
+    else return 32;
+}
+template <int NBK, bool BIG = false>
 __device__ __forceinline__ void stage_coarse_rows(float* coarse, const float* __restrict__ tab0, int n_mesh) {
     constexpr int W = 32 * NBK;
+    const int step = coarse_step<BIG>(n_mesh);
     for (int i = threadIdx.x; i < 64 * W; i += blockDim.x) {
         const int row = i / W, col = i % W;
-        coarse[row * kCoarseStride<NBK> + col] = tab0[(size_t)min(row * 32, n_mesh - 1) * W + col];
+        coarse[row * kCoarseStride<NBK> + col] = tab0[(size_t)min(row * step, n_mesh - 1) * W + col];
     }
     __syncthreads();
 }
-template <int NBK = 1>
+template <int NBK = 1, bool BIG = false>
 __device__ __forceinline__ float ispline_inverse(const float* __restrict__ tab0 /* [n_mesh][32 NBK], order 0 */, int n_mesh, int nb, float c,
                                                  float y, float tol, int hd, float (*ov)[64], int lane, const float* coarse) {
     constexpr int W = 32 * NBK;
@@ -1033,15 +1046,25 @@ __device__ __forceinline__ float ispline_inverse(const float* __restrict__ tab0 
         return acc;
     };
     auto spline_at = [&](int m) { return spline_row(reinterpret_cast<const float4_t*>(tab0 + (size_t)m * W)); };
-    // round 1: mesh points 0, 32, 64, ... (rows min(32 lane, last): the workgroup's LDS copy, kCoarseStride floats apart, when the caller staged one);
-    // round 2: the 32 points inside the interval found (weights beyond nb are zero)
+    // round 1: mesh points 0, step, 2 step, ... (step = 32 up to 2048 mesh points; rows min(step lane, last): the workgroup's LDS copy, kCoarseStride
+    // floats apart, when the caller staged one); round 2: the 32 points inside the interval found (weights beyond nb are zero)
     const int last = n_mesh - 1;
-    int m1 = min(lane * 32, last);
+    const int step = coarse_step<BIG>(n_mesh);
+    int m1 = min(lane * step, last);
     float g1 = coarse ? spline_row(reinterpret_cast<const float4_t*>(coarse + lane * kCoarseStride<NBK>)) : spline_at(m1);
     // (first lane whose mesh value exceeds y: robust against a rounding-level non-monotonicity of the fp32 sums)
-    int cnt = __ffsll((long long)~__ballot(g1 <= y && lane * 32 <= last)) - 1;
+    int cnt = __ffsll((long long)~__ballot(g1 <= y && lane * step <= last)) - 1;
     if (cnt < 0) cnt = 64;
-    const int base = max(cnt - 1, 0) * 32;
+    int base = max(cnt - 1, 0) * step;
+    // more than 2048 mesh points: the interval found holds step / 32 blocks of 32 points -- the last block whose first point does not exceed y
+    // (every lane reads the same row: the walk is wave-uniform)
+    if constexpr (BIG) {
+        const int end = min(base + step - 1, last);
+        for (int nxt = base + 32; nxt <= end; nxt += 32) {
+            if (!(spline_at(nxt) <= y)) break;
+            base = nxt;
+        }
+    }
     const int m2 = min(base + (lane & 31), last);
     const float g2 = spline_at(m2);
     cnt = __ffsll((long long)~__ballot(g2 <= y && lane < 32 && base + lane <= last)) - 1;
@@ -1080,7 +1103,7 @@ __device__ __forceinline__ float ispline_inverse(const float* __restrict__ tab0 
     return q / scale;
 }
 
-template <int D, int NBK = 1>
+template <int D, int NBK = 1, bool BIG = false>
 __device__ __forceinline__ void wave_serial_inverse(const ModelDev& md, const float* __restrict__ tabI, const float* __restrict__ gI, float (&cur)[D],
                                                     float (*vec)[64], float (*ov)[64], int lane, int exact, const float* coarse) {
     const int dl = NBK == 1 ? lane >> 5 : 0, j = NBK == 1 ? (lane & 31) : lane;
@@ -1119,7 +1142,7 @@ __device__ __forceinline__ void wave_serial_inverse(const ModelDev& md, const fl
                 }
                 const bool valid_d = (NBK == 1 ? 2 * p + dl : p) < D, valid = valid_d && j < nb;
                 const SigHead<R1> hdw = sigmoid_head<R1, NBK>(o, valid, valid_d, gI[j], md.i_reg, gate_i, R1{gq}, net.z[p * 64 + lane]);
-                cur[d] = ispline_inverse<NBK>(tabI, n_mesh, nb, hdw.c.c0, nxt[d], tol, hd, ov, lane, coarse);
+                cur[d] = ispline_inverse<NBK, BIG>(tabI, n_mesh, nb, hdw.c.c0, nxt[d], tol, hd, ov, lane, coarse);
             }
         } else {
 #pragma unroll
@@ -1148,7 +1171,7 @@ __device__ __forceinline__ void wave_serial_inverse(const ModelDev& md, const fl
 }
 
 // seed_mode 0: invert the latent points ug;  1: draw the latent points from the prior first (and report them)
-template <int D, int NBK = 1>
+template <int D, int NBK = 1, bool BIG = false>
 __global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(kOccSample, kOccSample))) void k_wave_sample(
     const ModelDev* __restrict__ mdp, const float* __restrict__ tabI, const float* __restrict__ tabP, const float* __restrict__ fk_nat, int draw,
     unsigned long long seed, const float* __restrict__ ug, int64_t B, float* __restrict__ xg, float* __restrict__ latent, int exact,
@@ -1158,7 +1181,7 @@ __global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(kOccSample,
     if (seed_offset_dev) seed += *seed_offset_dev * 0x9E3779B97F4A7C15ull;   // a device counter advances the stream (captured steps)
     const ModelDev& md = *mdp;
     const bool use_coarse = md.layer_kind == WF_LAYER_IMADE && md.n_layers > 0;
-    if (use_coarse) stage_coarse_rows<NBK>(coarse_s, tabI, md.isp.n_mesh);
+    if (use_coarse) stage_coarse_rows<NBK, BIG>(coarse_s, tabI, md.isp.n_mesh);
     const float* coarse = use_coarse ? coarse_s : nullptr;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float (*vec)[64] = lds[wv][0];
@@ -1272,7 +1295,7 @@ __global__ __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(kOccSample,
                     if (lane == d) latent[b * D + d] = cur[d];
             }
         }
-        wave_serial_inverse<D, NBK>(md, tabI, gI, cur, vec, ov, lane, exact, coarse);
+        wave_serial_inverse<D, NBK, BIG>(md, tabI, gI, cur, vec, ov, lane, exact, coarse);
 #pragma unroll
         for (int d = 0; d < D; ++d)
             if (lane == d) xg[b * D + d] = cur[d];
@@ -1378,9 +1401,14 @@ int launch_wave_sample(const ModelDev& md, const ModelDev* md_dev, const float* 
                        unsigned long long seed, const float* u, int64_t B, float* x, float* latent, int exact,
                        const unsigned long long* seed_offset_dev, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-#define CALLK(DD, K)                                                                                                                      \
-    hipLaunchKernelGGL((k_wave_sample<DD, K>), dim3(wave_grid(B)), dim3(kWB), 0, s, md_dev, tabI4, tabP4, fk_nat, draw, seed, u, B, x, latent, \
-                       exact, seed_offset_dev);                                                                                          \
+    // (the mesh search of the I-spline inverse reaches 2048 mesh points with its 32-point stride: larger meshes take the kernels built with the wider one)
+    const bool big = md.layer_kind == WF_LAYER_IMADE && md.n_layers > 0 && md.isp.n_mesh > kCoarseMeshMax;
+#define CALLB(DD, K, BIG)                                                                                                                       \
+    hipLaunchKernelGGL((k_wave_sample<DD, K, BIG>), dim3(wave_grid(B)), dim3(kWB), 0, s, md_dev, tabI4, tabP4, fk_nat, draw, seed, u, B, x, latent, \
+                       exact, seed_offset_dev)
+#define CALLK(DD, K)                 \
+    if (big) CALLB(DD, K, true);     \
+    else CALLB(DD, K, false);        \
     break
     if (md.nbp == 64) {
         switch (md.D) {
@@ -1406,6 +1434,7 @@ int launch_wave_sample(const ModelDev& md, const ModelDev* md_dev, const float* 
         default: return WF_ERR_UNSUPPORTED;
     }
 #undef CALLK
+#undef CALLB
     return finish();
 }
 

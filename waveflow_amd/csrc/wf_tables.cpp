@@ -240,6 +240,9 @@ int build_ortho_b(int k, int n_internal, int n_mesh, const double* Bt /* [4][nb]
                   double* ob_to_b) {
     const int nb = n_bases_of(WF_SPLINE_B, k, n_internal);
     if (nb % 2) return WF_ERR_NUMERIC;  // the reference exits on an odd basis count, ortho_splines.py:58-63
+    // fewer mesh points than bases: the Gram matrix of the sampled bases is singular, and Gram-Schmidt would normalise rounding residue (tables of
+    // 1e17 at 27 points for 28 bases) instead of failing
+    if (n_mesh < nb) return WF_ERR_NUMERIC;
     const int npair = nb / 2;
     const size_t plane = (size_t)nb * n_mesh;
     // Gram matrix of the sampled basis vectors (ovlp = mat.T @ mat, ortho_splines.py:65)
