@@ -1,0 +1,299 @@
+"""Stochastic reconfiguration as a whole step on the device (include/waveflow_sr_step.h, DeviceModel.sr_step, ModelTrainer.sr_on_device).
+
+The yardstick is the eager step (vqmc.train_step_sr) on the same walkers.  Inside the step, local energies, rows, Gram matrix, solve and apply
+are the entries the eager path calls; the two may differ only in the order of the fp64 mean of e_loc (about 1e-16 relative on the right-hand
+side).  The shifted matrix has a condition number of at most (trace + lambda) / lambda, about 1e3 B, so y moves by about 1e-11 and, after the one
+fp32 rounding of d, one ulp in a handful of entries of d.  Hence, elementwise,
+    |theta_step - theta_eager| <= 2^-23 |theta_eager| + 2^-22 lr |d_eager|
+(that ulp of d, and the two fp32 roundings of the update), and at most 1 % of the entries may differ at all: another forward kernel, re-derived
+local energies or a fused multiply-add in the update would break one of the two.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from conftest import sorted_walkers
+
+pytestmark = pytest.mark.gpu
+
+B_HE = 67
+LR = 1e-2
+SEED = 20240607
+FIRST = 5          # the counter the steps start from: ring slot 5
+_cache = {}
+
+
+def _waveflow(D, k, knots, layers, box, kind="mean", seed=7):
+    from waveflow_amd import model_factory
+    init = model_factory.get_waveflow_model(D, base_spline_degree=k, i_spline_degree=k, n_prior_internal_knots=knots, n_i_internal_knots=knots,
+                                            i_spline_reg=0.05, n_flow_layers=layers, box_size=box, xu_coord_type=kind)
+    return init(seed, D)
+
+
+def _he(he_flat):
+    """(params, psi, h_fn, x [67, 2] on the device, flat parameters on the device): the model and walkers of tests/test_gpu_sr.py."""
+    import torch
+    from waveflow_amd import checkpoint
+    from waveflow_amd.utils import physics
+    if "he" not in _cache:
+        params, psi, _, _ = _waveflow(2, 6, 23, 3, 10.0)
+        params = checkpoint.unflatten_like(params, he_flat)
+        protons, _ = physics.system_catalogue[1]["He"]
+        h_fn = physics.construct_hamiltonian_function(psi, protons=protons, n_space_dimensions=1, eps=0.0)
+        x = torch.as_tensor(sorted_walkers(B_HE, 2, 8.0, 5)).cuda()
+        _cache["he"] = (params, psi, h_fn, x, torch.as_tensor(np.asarray(he_flat, dtype=np.float32)).cuda())
+    return _cache["he"]
+
+
+def _three():
+    """A second shape: D = 3 (degree 6, 23 knots, 2 layers, box 10) at its initial parameters, 16 sorted walkers, two protons."""
+    import torch
+    from waveflow_amd import core
+    from waveflow_amd.utils import physics
+    if "three" not in _cache:
+        params, psi, _, _ = _waveflow(3, 6, 23, 2, 10.0)
+        protons, _ = physics.system_catalogue[1]["H2"]
+        h_fn = physics.construct_hamiltonian_function(psi, protons=protons, n_space_dimensions=1, eps=0.0)
+        x = torch.as_tensor(sorted_walkers(16, 3, 8.0, 5)).cuda()
+        _cache["three"] = (params, psi, h_fn, x, torch.as_tensor(core.flatten_params(params).astype(np.float32)).cuda())
+    return _cache["three"]
+
+
+def _fresh_state(model, flat0, lr=LR, first=FIRST, shifted=False, batch=B_HE):
+    """Parameters back at flat0 (a copy of their own), the model's images with them, and a train state whose poisoned workspace is allocated
+    here; `shifted`: 256 bytes into a larger allocation."""
+    import torch
+    xs = flat0.clone()
+    model.set_params_device(xs)
+    st = model.make_sr_train_state(xs, first, lr)
+    n = model.sr_step_workspace_bytes(batch)
+    buf = torch.full((n + 256,), 0xFF, dtype=torch.uint8, device=xs.device)
+    st["ws"] = buf[256:] if shifted else buf[:n]
+    return xs, st
+
+
+def _snapshot(xs, st):
+    import torch
+    torch.cuda.synchronize()
+    return {k: v.clone() for k, v in (("x", xs), ("ring", st["ring"]), ("norm_ring", st["norm_ring"]), ("status", st["status"]), ("counter", st["counter"]))}
+
+
+def _same(a, b):
+    import torch
+    return all(torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
+
+
+def _capture(model, step, restore):
+    """`step` captured once, the way ModelTrainer does it: a side stream, one call outside the capture, `restore()` to undo it, then the capture."""
+    import torch
+    side = torch.cuda.Stream(device=model.device)
+    side.wait_stream(torch.cuda.current_stream(model.device))
+    with torch.cuda.stream(side):
+        step()
+        restore()
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            step()
+    torch.cuda.current_stream(model.device).wait_stream(side)
+    return graph
+
+
+def _against_the_eager_step(case, tag):
+    import torch
+    from waveflow_amd import core, vqmc
+    params, psi, h_fn, x, flat0 = case
+    model, B = psi.model, int(x.shape[0])
+    dp = core.DeviceParams(params, flat0.clone(), 0)
+    d_eager, _ = vqmc.sr_natural_gradient(dp, psi, h_fn, x)
+    new_dp, loss_eager = vqmc.train_step_sr(1, psi, h_fn, dp, x, LR)
+    assert torch.equal(dp.flat, flat0)
+    xs, st = _fresh_state(model, flat0, batch=B)
+    model.sr_step(st, SEED, B, h_fn.protons, walkers=x)
+    torch.cuda.synchronize()
+    th_s, th_e, d = xs.double().cpu().numpy(), new_dp.flat.double().cpu().numpy(), d_eager.double().cpu().numpy()
+    bound = 2.0 ** -23 * np.abs(th_e) + 2.0 ** -22 * LR * np.abs(d)
+    diff = np.abs(th_s - th_e)
+    n_diff = int((diff != 0).sum())
+    worst = float((diff / np.maximum(bound, 1e-300)).max())
+    ring, norm, status = st["ring"].cpu().numpy(), st["norm_ring"].cpu().numpy(), st["status"].cpu().tolist()
+    want_norm = float((d * d).sum())
+    print(f"[sr step vs eager, {tag}] B {B} P {model.n_params}: {n_diff} entries differ (cap {model.n_params // 100}), worst |diff| / bound {worst:.3f}; "
+          f"loss {ring[FIRST, 0] / B:.12f} vs {loss_eager:.12f}; |d|^2 {norm[FIRST]:.9e} vs {want_norm:.9e}; status {status}")
+    assert np.isfinite(th_s).all() and not np.array_equal(th_s, flat0.double().cpu().numpy())
+    assert (diff <= bound).all()
+    assert n_diff <= model.n_params // 100
+    assert abs(ring[FIRST, 0] / B - loss_eager) <= 1e-12 * max(1.0, abs(loss_eager)) and ring[FIRST, 2] == B
+    assert status == [0, 0]
+    assert abs(norm[FIRST] - want_norm) <= 2.0 ** -20 * want_norm
+    assert int(st["counter"].item()) == FIRST + 1
+    assert not ring[np.arange(ring.shape[0]) != FIRST].any() and not norm[np.arange(norm.shape[0]) != FIRST].any()
+
+
+def test_step_on_given_walkers_is_the_eager_step_he(he_flat):
+    _against_the_eager_step(_he(he_flat), "He")
+
+
+def test_step_on_given_walkers_is_the_eager_step_three_particles():
+    _against_the_eager_step(_three(), "D = 3")
+
+
+def test_three_steps_are_bitwise_repeatable_direct_shifted_and_replayed(he_flat):
+    """Three consecutive steps on walkers the step draws, from the same start: direct calls, direct calls with the workspace at another address, and
+    one captured step replayed three times."""
+    import torch
+    params, psi, h_fn, x, flat0 = _he(he_flat)
+    model = psi.model
+    out = {}
+    for mode in ("direct", "shifted", "graph"):
+        xs, st = _fresh_state(model, flat0, shifted=mode == "shifted")
+
+        def step():
+            model.sr_step(st, SEED, B_HE, h_fn.protons)
+
+        def restore():
+            xs.copy_(flat0)
+            model.set_params_device(xs)
+            st["counter"].fill_(FIRST)
+            for name in ("ring", "norm_ring", "status"):
+                st[name].zero_()
+        run = _capture(model, step, restore).replay if mode == "graph" else step
+        for _ in range(3):
+            run()
+        out[mode] = _snapshot(xs, st)
+    a = out["direct"]
+    assert int(a["counter"].item()) == FIRST + 3 and a["status"].tolist() == [0, 0]
+    assert bool((a["ring"][FIRST:FIRST + 3, 2] == B_HE).all()) and bool((a["norm_ring"][FIRST:FIRST + 3] > 0).all())
+    assert len({float(v) for v in a["ring"][FIRST:FIRST + 3, 0]}) == 3            # three batches of walkers
+    assert not torch.equal(a["x"], flat0)
+    assert _same(a, out["shifted"])
+    assert _same(a, out["graph"])
+
+
+def test_drawn_walkers_are_written_and_give_the_same_step_when_fed_back(he_flat):
+    import torch
+    params, psi, h_fn, x, flat0 = _he(he_flat)
+    model = psi.model
+    xs, st = _fresh_state(model, flat0)
+    w5 = torch.full((B_HE, 2), float("nan"), device="cuda")
+    model.sr_step(st, SEED, B_HE, h_fn.protons, out_walkers=w5)
+    drew = _snapshot(xs, st)
+    w6 = torch.full((B_HE, 2), float("nan"), device="cuda")
+    model.sr_step(st, SEED, B_HE, h_fn.protons, out_walkers=w6)      # counter 6, from the moved parameters
+    xs2, st2 = _fresh_state(model, flat0)
+    model.sr_step(st2, SEED + 1, B_HE, h_fn.protons, walkers=w5)      # (the seed is not used when the walkers are given)
+    fed = _snapshot(xs2, st2)
+    assert _same(drew, fed)
+    xs3, st3 = _fresh_state(model, flat0, first=FIRST + 1)
+    w6b = torch.full((B_HE, 2), float("nan"), device="cuda")
+    model.sr_step(st3, SEED, B_HE, h_fn.protons, out_walkers=w6b)     # counter 6 from the start: other walkers than counter 5
+    torch.cuda.synchronize()
+    for w in (w5, w6, w6b):
+        assert bool(torch.isfinite(w).all()) and bool((w[:, 1] >= w[:, 0]).all()) and float(w.abs().max()) <= 10.0
+    assert not torch.equal(w5, w6) and not torch.equal(w5, w6b)
+
+
+def test_learning_rate_is_read_on_the_device_at_every_replay(he_flat):
+    import torch
+    params, psi, h_fn, x, flat0 = _he(he_flat)
+    model = psi.model
+    xs, st = _fresh_state(model, flat0, lr=0.0)
+
+    def restore():   # (the call outside the capture ran at learning rate 0: only the bookkeeping moved)
+        st["counter"].fill_(FIRST)
+        for name in ("ring", "norm_ring", "status"):
+            st[name].zero_()
+    graph = _capture(model, lambda: model.sr_step(st, SEED, B_HE, h_fn.protons), restore)
+    graph.replay()
+    s = _snapshot(xs, st)
+    assert torch.equal(s["x"].view(torch.int32), flat0.view(torch.int32))
+    assert int(s["counter"].item()) == FIRST + 1 and float(s["ring"][FIRST, 2]) == B_HE and s["status"].tolist() == [0, 0] and float(s["norm_ring"][FIRST]) > 0
+    st["step_size"].fill_(LR)
+    graph.replay()
+    s2 = _snapshot(xs, st)
+    assert not torch.equal(s2["x"], flat0) and bool(torch.isfinite(s2["x"]).all())
+    assert int(s2["counter"].item()) == FIRST + 2 and float(s2["ring"][FIRST + 1, 2]) == B_HE and s2["status"].tolist() == [0, 0]
+
+
+def test_a_refused_solve_skips_the_update_and_is_counted(he_flat):
+    """batch = 1, relative damping only: the centred 1 x 1 matrix and its shift are exactly 0 -- info = 1 (tests/test_gpu_sr.py), a status, no fault."""
+    import torch
+    params, psi, h_fn, x, flat0 = _he(he_flat)
+    model = psi.model
+    xs, st = _fresh_state(model, flat0, batch=B_HE)   # (the workspace of 67 walkers holds the one-walker step as well)
+    model.sr_step(st, SEED, 1, h_fn.protons, damping=0.0, relative_damping=1e-3)
+    s = _snapshot(xs, st)
+    assert torch.equal(s["x"].view(torch.int32), flat0.view(torch.int32))
+    assert s["status"].tolist() == [1, 1]
+    assert int(s["counter"].item()) == FIRST + 1 and float(s["ring"][FIRST, 2]) == 1.0 and bool(torch.isfinite(s["ring"][FIRST]).all())
+    assert bool(torch.isnan(s["norm_ring"][FIRST]))
+    model.sr_step(st, SEED, B_HE, h_fn.protons)
+    s2 = _snapshot(xs, st)
+    assert s2["status"].tolist() == [0, 1] and not torch.equal(s2["x"], flat0) and bool(torch.isfinite(s2["x"]).all())
+    assert int(s2["counter"].item()) == FIRST + 2 and float(s2["ring"][FIRST + 1, 2]) == B_HE
+
+
+def test_refusals_of_the_c_entries_with_a_model(he_flat):
+    import torch
+    from waveflow_amd import sr
+    params, psi, h_fn, x, flat0 = _he(he_flat)
+    model = psi.model
+    xs, st = _fresh_state(model, flat0)
+    L = sr.lib()
+    pr, n_pr = model._protons(h_fn.protons)
+    ws, n = st["ws"].data_ptr(), st["ws"].numel()
+    assert n == L.wf_vqmc_sr_step_workspace_bytes(model._h, B_HE) and n > B_HE * model.n_params * 4 + B_HE * B_HE * 8
+    assert L.wf_vqmc_sr_step_workspace_bytes(model._h, 4096) > 0
+    assert L.wf_vqmc_sr_step_workspace_bytes(model._h, 4097) == -2
+    c = ctypes.byref(st["c"])
+    assert L.wf_vqmc_sr_step(model._h, c, SEED, 4097, pr, n_pr, 0.0, 1e-3, 0, None, 1, ws, 1 << 40, None) == -2
+    assert L.wf_vqmc_sr_step(model._h, c, SEED, B_HE, pr, n_pr, 0.0, 1e-3, 0, None, 1, ws, n - 1, None) == -1
+    assert L.wf_vqmc_sr_step(model._h, c, SEED, B_HE, pr, n_pr, 0.0, 1e-3, 0, None, 0, ws, n, None) == -1
+    assert L.wf_vqmc_sr_step(model._h, c, SEED, B_HE, pr, n_pr, 0.0, 0.0, 0, None, 1, ws, n, None) == -1
+    s = _snapshot(xs, st)   # nothing was launched
+    assert torch.equal(s["x"], flat0) and int(s["counter"].item()) == FIRST and not bool(s["ring"].any()) and s["status"].tolist() == [0, 0]
+
+
+def test_model_trainer_with_sr_on_the_device(tmp_path):
+    import torch
+    from waveflow_amd import vqmc
+
+    def trainer(name, lr=1e-3):
+        t = vqmc.ModelTrainer(system_name="He", learning_rate=lr, box_length=10, num_epochs=3, batch_size=64)
+        t.save_dir = str(tmp_path / name)
+        t.optimizer = 'sr'
+        t.sr_on_device = True
+        return t
+
+    t = trainer("a")
+    _, loss = t.start_training(verbose=False)
+    assert len(loss[1:]) == 3 and np.isfinite(np.asarray(loss[1:], dtype=np.float64)).all()
+    for f in ("checkpoints", "loss.npy", "energies.npy", "system_info.json", "outputs/wavefunctions_2d/values_epoch1.npy",
+              "outputs/sample_points/values_epoch1.npy", "outputs/density_1e/onproton_values_epoch1.npy"):
+        assert os.path.exists(os.path.join(t.save_dir, f)), f
+    assert not os.path.exists(os.path.join(t.save_dir, "optimizer_state.npz"))
+    final = t.params.flat.clone()
+    t2 = trainer("b")
+    _, loss2 = t2.start_training(verbose=False)
+    assert loss2 == loss and torch.equal(t2.params.flat, final)
+    # a schedule is called per epoch and honoured: rate 0 leaves the parameters at their initial values, which a rate of 1e-3 moved
+    seen = []
+
+    def zero(epoch):
+        seen.append(epoch)
+        return 0.0
+    t3 = trainer("c", lr=zero)
+    t3.use_graph = False      # the same loop, call by call
+    _, loss3 = t3.start_training(verbose=False)
+    t4 = trainer("d", lr=zero)
+    _, loss4 = t4.start_training(verbose=False)
+    assert seen == [1, 2, 3, 1, 2, 3]
+    rng = np.random.default_rng(t4.seed)   # (start_training's first draw seeds the model)
+    initial = vqmc.create_train_state(t4.box_length, 0.0, n_particle=t4.n_particle, rng=int(rng.integers(1 << 31)), xu_coord_type=t4.xu_coord_type,
+                                      spline_degree=t4.spline_degree, num_knots=t4.num_knots, n_flow_layers=t4.n_flow_layer)[3].x
+    assert torch.equal(t3.params.flat.view(torch.int32), initial.view(torch.int32)) and torch.equal(t4.params.flat.view(torch.int32), initial.view(torch.int32))
+    assert not torch.equal(final, initial)
+    # (the first epoch's walkers and parameters are those of trainer "a": the same first loss, bit for bit)
+    assert loss4[1] == loss[1] == loss3[1] and len(loss4[1:]) == 3 and len(loss3[1:]) == 3

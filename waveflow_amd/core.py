@@ -457,6 +457,46 @@ class DeviceModel:
         self._run("wf_mle_train_step", ctypes.byref(st["c"]), self._p(x), n, float(step_size), float(b1), float(b2), float(eps), *ws)
         self._invalidate_host_copy()
 
+    # ---- stochastic reconfiguration as a whole step on the device (include/waveflow_sr_step.h)
+    def make_sr_train_state(self, x, first_step, learning_rate, ring_len=128, defer_eval_tables=False):
+        """Device-side state of wf_vqmc_sr_step around the parameter vector x (float32 cuda, updated in place): the step counter, the learning
+        rate ("step_size": one float32 on the device, rewritten between steps or graph replays with .fill_), the loss ring [ring_len, 3], the
+        ring of |d|^2 ("norm_ring") and "status" = [the solver's info of the last step, steps skipped so far]."""
+        torch = _torch()
+        from . import sr
+        if not x.is_cuda or str(x.dtype) != "torch.float32" or not x.is_contiguous() or x.numel() != self.n_params:
+            raise ValueError(f"expected a contiguous float32 cuda vector of {self.n_params} parameters")
+        if int(ring_len) < 1:
+            raise ValueError("ring_len must be >= 1")
+        dev = x.device
+        st = {"x": x, "ring_len": int(ring_len),
+              "counter": torch.tensor([int(first_step)], dtype=torch.int64, device=dev),
+              "step_size": torch.tensor([float(learning_rate)], dtype=torch.float32, device=dev),
+              "ring": torch.zeros(int(ring_len), 3, dtype=torch.float64, device=dev),
+              "norm_ring": torch.zeros(int(ring_len), dtype=torch.float64, device=dev),
+              "status": torch.zeros(2, dtype=torch.int32, device=dev)}
+        st["c"] = sr.SrTrainState(x.data_ptr(), st["counter"].data_ptr(), st["step_size"].data_ptr(), st["ring"].data_ptr(),
+                                  st["norm_ring"].data_ptr(), st["status"].data_ptr(), int(ring_len), int(bool(defer_eval_tables)))
+        return st
+
+    def sr_step_workspace_bytes(self, batch):
+        """Workspace of sr_step for `batch` walkers per step; WfError where the library has no such step for this model or batch."""
+        from . import sr
+        return _lib.check(sr.lib().wf_vqmc_sr_step_workspace_bytes(self._h, int(batch)), "wf_vqmc_sr_step_workspace_bytes")
+
+    def sr_step(self, st, seed, batch, protons, damping=0.0, relative_damping=1e-3, exact_sampler=False, walkers=None, out_walkers=None):
+        """One whole stochastic-reconfiguration step on the device (wf_vqmc_sr_step): no host work, no wait, capturable in a hipGraph.
+        The step draws its walkers (out_walkers [batch, D], if given, receives them) or reads them from `walkers` [batch, D]; the learning
+        rate is st["step_size"].  Arguments are checked before anything is launched (ValueError)."""
+        from . import sr
+        damping, relative_damping = sr._check_step(batch, self.D, damping, relative_damping, walkers, out_walkers)
+        ws = self._train_ws(st, self.sr_step_workspace_bytes(batch))
+        x = walkers if walkers is not None else out_walkers
+        _lib.check(sr.lib().wf_vqmc_sr_step(self._h, ctypes.byref(st["c"]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(batch), *self._protons(protons),
+                                            damping, relative_damping, int(bool(exact_sampler)), self._p(x), int(walkers is None), *ws,
+                                            self._stream()), "wf_vqmc_sr_step")
+        self._invalidate_host_copy()
+
     def block_sums(self, v):
         """fp64 [sum v, sum v^2, count] on the device (deterministic order)."""
         torch = _torch()

@@ -281,6 +281,12 @@ int64_t block_sums_ws_bytes(int64_t B);
 constexpr int kModePresort = 4;   // bit of launch_mfma's mode: sort each row in registers, psi gets (-1)^inversions (wf_mfma_impl.h)
 int launch_sort_rows(const float* x, int64_t B, int D, float* xs, int32_t* inv, void* stream);
 int launch_apply_sign(float* v, const int32_t* inv, int64_t B, void* stream);
+// the glue of wf_vqmc_sr_step (wf_kernels_sr_step.hip): inv = 1 / (psi + 1e-8), e_loc = hpsi inv, rhs = e_loc - mean(e_loc) in fp64 (B <= 4096);
+// |d|^2 in fp64 with the step's verdict (flag[0] = 1: update; status and norm ring as include/waveflow_sr_step.h); the guarded update
+int launch_sr_eloc_rhs(const float* hpsi, const float* psi, int64_t B, float* e_loc, float* inv, double* rhs, void* stream);
+int launch_sr_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, int ring_len,
+                      const unsigned long long* counter, void* stream);
+int launch_sr_update(float* params, const float* d, int64_t P, const float* step_size, const int32_t* flag, void* stream);
 
 void set_hip_error(int e);
 

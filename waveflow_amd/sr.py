@@ -1,5 +1,6 @@
 """Stochastic reconfiguration (the natural gradient of variational Monte Carlo) from per-walker Jacobian rows, in its B x B ("minSR") form:
-the ctypes surface of include/waveflow_sr.h.
+the ctypes surface of include/waveflow_sr.h, and of include/waveflow_sr_step.h (the whole training step on the device: STEP_PROTOTYPES,
+SrTrainState; core.DeviceModel.sr_step drives it).
 
 With O[b][k] = d ln psi_b / d theta_k, local energies e, H = I - 1 1^T / B and lambda > 0,
     d = (O^T H O / B + lambda I)^-1 (2 / B) O^T H e  =  (2 / B) O^T H y,    (H O O^T H / B + lambda I) y = H e
@@ -23,6 +24,19 @@ PROTOTYPES = {
     "wf_sr_apply": (_i32, [_vp, _i64, _i64, _i64, _vp, _f64, _vp] + _ws + [_vp]),
 }
 
+
+class SrTrainState(ctypes.Structure):
+    """wf_sr_train_state (include/waveflow_sr_step.h)"""
+    _fields_ = [("params_dev", _vp), ("counter_dev", _vp), ("step_size_dev", _vp), ("loss_ring_dev", _vp), ("norm_ring_dev", _vp),
+                ("status_dev", _vp), ("ring_len", ctypes.c_int32), ("defer_eval_tables", ctypes.c_int32)]
+
+
+# name -> (restype, argtypes): every function of include/waveflow_sr_step.h, in its order (tests/test_sr_step_host.py)
+STEP_PROTOTYPES = {
+    "wf_vqmc_sr_step_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_vqmc_sr_step": (_i32, [_vp, ctypes.POINTER(SrTrainState), ctypes.c_uint64, _i64, _vp, _i32, _f64, _f64, _i32, _vp, _i32] + _ws + [_vp]),
+}
+
 _bound = None
 
 
@@ -35,11 +49,11 @@ class NotPositiveDefinite(ArithmeticError):
 
 
 def lib():
-    """The handle of _lib.lib() with PROTOTYPES applied to it."""
+    """The handle of _lib.lib() with PROTOTYPES and STEP_PROTOTYPES applied to it."""
     global _bound
     L = _lib.lib()
     if _bound is not L:
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(STEP_PROTOTYPES.items()):
             f = getattr(L, name)
             f.restype = restype
             f.argtypes = argtypes
@@ -55,6 +69,28 @@ def _check_damping(damping, relative_damping):
         raise ValueError(f"damping and relative_damping must be >= 0, got {damping} and {relative_damping}")
     if damping == 0.0 and relative_damping == 0.0:
         raise ValueError("damping and relative_damping are both zero: the centred B x B matrix is singular without a shift")
+    return damping, relative_damping
+
+
+def _check_step(batch, n_dim, damping, relative_damping, walkers, out_walkers):
+    """The arguments of one device-side training step (core.DeviceModel.sr_step) -> (damping, relative_damping); `walkers` (read) and
+    `out_walkers` (written) are contiguous float32 cuda tensors [batch, n_dim] or None, and at most one of them is given."""
+    import torch
+    damping, relative_damping = _check_damping(damping, relative_damping)
+    batch = int(batch)
+    if batch < 1 or batch > MAX_WALKERS:
+        raise ValueError(f"{batch} walkers per step: the B x B solve is built for 1 .. {MAX_WALKERS}")
+    if walkers is not None and out_walkers is not None:
+        raise ValueError("walkers (the step reads them) and out_walkers (the step writes what it drew) exclude each other")
+    for what, t in (("walkers", walkers), ("out_walkers", out_walkers)):
+        if t is None:
+            continue
+        if not hasattr(t, "is_cuda") or t.dim() != 2 or tuple(t.shape) != (batch, int(n_dim)):
+            raise ValueError(f"{what} must be a torch tensor of shape [{batch}, {int(n_dim)}]")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous float32, got {t.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"{what} must be a cuda tensor: stochastic reconfiguration has no CPU fallback")
     return damping, relative_damping
 
 

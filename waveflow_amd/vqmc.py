@@ -330,8 +330,9 @@ class ModelTrainer:
         self.use_graph = True  # single process: capture the whole step (wf_vqmc_train_step) in a hipGraph and replay it
         self.seed = 2          # vqmc.py:57: PRNGKey(2)
         self.exact_sampler = False   # False: the reference's sampler (made.py:88 quirk); True: draws from |psi|^2
-        self.optimizer = 'adam'      # 'sr': stochastic reconfiguration steps (train_step_sr), eager, one process
+        self.optimizer = 'adam'      # 'sr': stochastic reconfiguration steps (train_step_sr; eager unless sr_on_device), one process
         self.sr_damping = {}         # damping / relative_damping of train_step_sr (its defaults when empty)
+        self.sr_on_device = False    # optimizer='sr' only: True runs the whole step on the device (wf_vqmc_sr_step), captured once when use_graph
 
     def start_training(self, restart=False, verbose=True, group=None):
         """Under torch.distributed (one process per GPU, `torchrun examples/run_vqmc.py`) the walkers of a step are split over
@@ -386,7 +387,8 @@ class ModelTrainer:
         # per step, no such limit where the staged large-batch sampler applies); otherwise the host-stepped loop below (sampler, loss + gradient, Adam: three library calls per step)
         # Sharded over several processes: the same sequence in two halves around the step's one all-reduce.
         if optimizer == 'sr':
-            params = self._train_sr(psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose)
+            train = self._train_sr_device if getattr(self, "sr_on_device", False) else self._train_sr
+            params = train(psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose)
             self.params, self.loss, self.energies = params, loss, energies
             self.psi, self.log_pdf, self.sample, self.h_fn = psi, log_pdf, sample, h_fn
             return params, loss
@@ -441,6 +443,86 @@ class ModelTrainer:
             loss.append(new_loss)
             energies.append([new_loss])
         return params
+
+    def _train_sr_device(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose):
+        """optimizer='sr' with sr_on_device: the loop of _train_graphed around wf_vqmc_sr_step.  Per epoch one graph launch (use_graph) or one
+        library call; the learning rate is a device scalar, rewritten before the step when `learning_rate` is a schedule; the host looks at the
+        loss ring every 100 epochs and at checkpoints, and at the step's status with it: steps the solver refused (a pivot that is not positive,
+        a step that is not finite) leave the parameters as they are and are reported once, with their count.  `loss` and `energies` grow in place."""
+        import warnings
+        import torch
+        model = psi.model
+        lr = self.learning_rate
+        lr_at = (lambda e: float(lr(e))) if callable(lr) else (lambda e: float(lr))
+        damping = getattr(self, "sr_damping", {})
+        batch = int(self.batch_size)
+        st = model.make_sr_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True)
+        model.set_params_device(opt_state.x)
+        seed = int(rng.integers(1 << 62))
+
+        def step():
+            model.sr_step(st, seed, batch, h_fn.protons, exact_sampler=self.exact_sampler, **damping)
+        st["ws"] = model._workspace(model.sr_step_workspace_bytes(batch), opt_state.x.device)   # allocated here, outside the capture
+        replay = step
+        if self.use_graph:
+            side = torch.cuda.Stream(device=model.device)
+            side.wait_stream(torch.cuda.current_stream(model.device))
+            try:
+                with torch.cuda.stream(side):
+                    # one step outside the capture (every kernel of the sequence has run once before it is recorded) at learning rate 0: the
+                    # parameters come out bitwise as they went in; what it left in the counter, the rings and the status is put back
+                    step()
+                    st["counter"].fill_(start_epoch + 1)
+                    for name in ("ring", "norm_ring", "status"):
+                        st[name].zero_()
+                    side.synchronize()
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=side):
+                        step()
+                replay = graph.replay
+            except Exception as e:
+                raise RuntimeError("hipGraph capture of the stochastic-reconfiguration step failed") from e
+            torch.cuda.current_stream(model.device).wait_stream(side)
+        fetched = [start_epoch]   # losses of the epochs up to here are on the host
+        warned = [False]
+
+        def fetch(upto):
+            torch.cuda.synchronize(model.device)
+            ring = st["ring"].cpu().numpy()
+            new = [float(ring[e % st["ring_len"], 0] / ring[e % st["ring_len"], 2]) for e in range(fetched[0] + 1, upto + 1)]
+            fetched[0] = upto
+            info, skipped = (int(v) for v in st["status"].cpu().tolist())
+            if skipped and not warned[0]:
+                warned[0] = True
+                warnings.warn(f"stochastic reconfiguration: {skipped} of the first {upto - start_epoch} steps were skipped (status of the last step: "
+                              f"{info}; > 0: that pivot of the shifted B x B matrix is not positive, -1: the step is not finite) -- more damping")
+            return new
+
+        params = get_params(opt_state)
+        for epoch in range(start_epoch + 1, start_epoch + self.num_epochs + 1):
+            if epoch % self.log_every == 0 or epoch == 1:
+                new = fetch(epoch - 1)
+                loss.extend(new)
+                energies.extend([[v] for v in new])
+                opt_state.version += 1
+                params = get_params(opt_state)
+                helpers.create_checkpoint_wavefunc(int(rng.integers(1 << 31)), save_dir, psi, sample, params, epoch, loss, energies, system_dict)
+                model.set_params_device(opt_state.x)
+            if callable(lr) or epoch == start_epoch + 1:
+                st["step_size"].fill_(lr_at(epoch))
+            replay()
+            if epoch % 100 == 0:
+                new = fetch(epoch)
+                loss.extend(new)
+                energies.extend([[v] for v in new])
+                if epoch % self.log_every == 0 and verbose:
+                    print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
+        new = fetch(start_epoch + self.num_epochs)
+        loss.extend(new)
+        energies.extend([[v] for v in new])
+        opt_state.version += 1
+        model.set_params_device(opt_state.x)   # every image of the model, evaluation tables included, holds the final parameters
+        return get_params(opt_state)
 
     def _train_graphed(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose,
                        group=None, rank=0, local_batch=None):
