@@ -93,22 +93,15 @@ def main():
                 device_step("direct")
 
         model.set_params_device(states["graph"][0])
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            device_step("graph")   # (outside the capture: every kernel of the sequence has run once)
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                device_step("graph")
-        torch.cuda.current_stream().wait_stream(side)
+        # (one step outside the capture: every kernel of the sequence has run once)
+        replay = vqmc.capture_step(model, lambda: device_step("graph"), warm_up=lambda: device_step("graph"))
 
         def graph_steps(n):
             # (the model's images follow whichever parameter vector stepped last: hand them back to this variant's, as a trainer that shares
             # a model between optimisers would)
             model.set_params_device(states["graph"][0])
             for _ in range(n):
-                graph.replay()
+                replay()
 
         variants = {"eager": eager_steps, "direct": direct_steps, "graph": graph_steps}
 
@@ -141,7 +134,7 @@ def main():
         r["skipped_steps"] = {k: int(states[k][1]["status"][1].item()) for k in states}
         r["finite"] = {"eager": bool(torch.isfinite(eager["flat"]).all()), **{k: bool(torch.isfinite(states[k][0]).all()) for k in states}}
         print(json.dumps(r), flush=True)
-        del graph, states, eager
+        del replay, states, eager
         torch.cuda.empty_cache()
 
 

@@ -13,7 +13,7 @@ import numpy as np
 from . import flows
 from .model_factory import get_masked_transform
 from .utils import helpers
-from .vqmc import adam
+from .vqmc import adam, capture_step, loss_ring_reader, run_device_loop
 
 
 def get_dataset(dataset_name, n_samples, margin, rng=None):
@@ -104,41 +104,22 @@ def train_model(target, num_epochs, n_model_sample, model_type='IFlow', dataset_
     metrics = ([], [], [])   # KDE KL divergences, KDE Hellinger distances, reconstruction distances
     model = log_pdf.model
     # every epoch is the same sequence of launches on resident data: capture it once (wf_mle_train_step) and replay it; the
-    # host reads the loss ring at checkpoints and every `ring` epochs
+    # host reads the loss ring at checkpoints and every `ring` epochs (and, when it reports, after every check_step-th epoch)
     ring = 256
     st = model.make_train_state(state.x, state.m, state.v, 1, ring_len=ring, defer_eval_tables=True)   # refreshed before every evaluation below
     model.set_params_device(state.x)
     st["ws"] = model._workspace(model.mle_train_step_workspace_bytes(x_dev.shape[0]), x_dev.device)
-    side = torch.cuda.Stream(device=model.device)
-    side.wait_stream(torch.cuda.current_stream(model.device))
-    with torch.cuda.stream(side):
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            model.mle_train_step(st, x_dev, step_size)
-    torch.cuda.current_stream(model.device).wait_stream(side)
-    fetched = [0]
+    replay = capture_step(model, lambda: model.mle_train_step(st, x_dev, step_size))
 
-    def fetch(upto):
-        torch.cuda.synchronize(model.device)
-        r = st["ring"].cpu().numpy()
-        losses.extend(float(-r[e % ring, 0] / r[e % ring, 2]) for e in range(fetched[0] + 1, upto + 1))
-        fetched[0] = upto
+    def checkpoint(epoch, params):
+        helpers.make_checkpoint_benchmark(int(g.integers(1 << 31)), params, log_pdf, sample, losses, *metrics,
+                                          n_model_sample=n_model_sample, save_dir=run_dir, epoch=epoch, ngrid=ngrid)
 
-    for epoch in range(1, num_epochs + 1):
-        if epoch == 1 or epoch % check_step == 0:
-            fetch(epoch - 1)
-            state.version += 1
-            helpers.make_checkpoint_benchmark(int(g.integers(1 << 31)), get_params(state), log_pdf, sample, losses, *metrics,
-                                              n_model_sample=n_model_sample, save_dir=run_dir, epoch=epoch, ngrid=ngrid)
-            model.set_params_device(state.x)
-        # (the reference permutes the target rows here; the full-batch mean does not depend on their order)
-        graph.replay()
-        if epoch % ring == 0:
-            fetch(epoch)
+    def fetched(epoch, new):
+        losses.extend(new)
         if verbose and epoch % check_step == 0:
-            fetch(epoch)
             print(f"Epoch {epoch} | loss: {losses[-1]}")
-    fetch(num_epochs)
-    state.version += 1
-    model.set_params_device(state.x)   # every image, evaluation tables included, holds the final parameters
-    return get_params(state), losses
+    # (the reference permutes the target rows every epoch; the full-batch mean does not depend on their order)
+    params = run_device_loop(model, state, get_params, replay, loss_ring_reader(model, st, 1, sign=-1.0), losses.extend, 1, num_epochs, check_step,
+                             checkpoint, ring, fetched, report_every=check_step if verbose else 0)
+    return params, losses

@@ -16,12 +16,20 @@ static int check_fwd(const wf_model* m, const void* x, int64_t B, const void* ou
     if (!m->params_set && m->n_params > 0) return WF_ERR_INVALID;
     return WF_OK;
 }
+// the models the reverse sweeps cover; second_order: psi and its Laplacian (Waveflow prior, IMADE layers)
+bool grad_supported(const wf_model* m, bool second_order) { return m->d_grad_map && (!second_order || m->grad_psi_ok); }
 // ... and every gradient entry point: the gradient is written for an empty batch too; second_order: psi and its Laplacian (wf_psi_vjp, wf_vqmc_loss_grad)
 static int check_grad(const wf_model* m, const void* x, int64_t B, const void* grad, bool second_order) {
     int rc = check_fwd(m, x, B, grad);
     if (rc) return rc;
     if (!grad) return WF_ERR_INVALID;
-    if (!m->d_grad_map || (second_order && !m->grad_psi_ok)) return WF_ERR_UNSUPPORTED;
+    return grad_supported(m, second_order) ? WF_OK : WF_ERR_UNSUPPORTED;
+}
+// What wf_hamiltonian_fwd and wf_psi_coord_derivs refuse beyond check_fwd, in this order
+int check_energy_model(const wf_model* m) {
+    if (m->desc.prior_kind != WF_PRIOR_WAVEFLOW) return WF_ERR_INVALID;
+    if (!m->wave_ok || !m->d_tabP3 || !m->d_grad_fk) return WF_ERR_UNSUPPORTED;
+    if (m->desc.n_flow_layers > 0 && m->desc.layer_kind != WF_LAYER_IMADE) return WF_ERR_UNSUPPORTED;
     return WF_OK;
 }
 // proton positions of the Hamiltonian (at most 8, on the host); false: invalid arguments
@@ -66,7 +74,7 @@ static bool energy_dir_capable_at(const wf_model* m, int64_t B) {
 }
 // the matrix-core gradient path (wf_kernels_etile_bwd.hip): D = 2, <= 64 bases; WF_GRAD_TILE_MIN (read per call).  d_egacc: the gradient blocks
 // grad_prepare allocates where the path exists; gates and the one-kernel form are energy_vjp_capable's business
-bool grad_tile_capable_at(const wf_model* m, int64_t B) {
+static bool grad_tile_capable_at(const wf_model* m, int64_t B) {
     if (!m->d_egacc) return false;
     return at_least(B, env_grad_tile_min()) && m->desc.n_dim == 2 && (m->nbp == 32 || m->nbp == 64) && mc_family(m) && m->desc.prior_kind == WF_PRIOR_WAVEFLOW &&
            m->d_tabI4c && m->d_tabP4c && energy_vjp_capable(&m->mdev);
@@ -74,14 +82,26 @@ bool grad_tile_capable_at(const wf_model* m, int64_t B) {
 // Large batches of the two-particle family (the family of the matrix-core local energy, <= 64 bases): the staged inverse / sampler of
 // wf_kernels_etile_sample.hip (conditioners on the matrix cores, one lane per walker for the searches).  WF_SAMPLE_TILE_MIN (read per call) moves the switch
 // point; 0 disables the path.  It reads the MFMA image and the composite dimension-0 tables: not while they are stale (deferred training steps).
-bool tile_sample_capable_at(const wf_model* m, int64_t B) {
+static bool tile_sample_capable_at(const wf_model* m, int64_t B) {
     const wf_model_desc& d = m->desc;
     // (the piecewise-constant envelope of k_tsample's second prior column takes the maximum over at most 9 coefficients per knot interval:
     // prior degrees above 8 keep the wave / one-lane samplers, whose bound is the global one)
     return at_least(B, env_sample_tile_min()) && d.n_dim == 2 && m->nbp == 32 * m->mdev.nbk && mc_family(m) && d.prior_kind == WF_PRIOR_WAVEFLOW && d.p_degree <= 8 &&
            m->d_tabI4 && m->d_tabP3 && m->dev.b_to_ob && m->d_grad_fk && tile_sample_capable(&m->mdev);
 }
-bool tile_sample_ok(const wf_model* m, int64_t B) { return tile_sample_capable_at(m, B) && tiles_fresh(m); }
+static bool tile_sample_ok(const wf_model* m, int64_t B) { return tile_sample_capable_at(m, B) && tiles_fresh(m); }
+
+// Does a training step of B walkers read the evaluation tables (the MFMA image, the composite tables)?  At a batch size of the matrix-core sampler
+// or gradient it does, and then refreshes them whatever defer_eval_tables says: a hipGraph of the step replays the kernels chosen at capture, and a
+// deferred refresh would leave them on stale tables from the second replay on.  (Capability, not tiles_fresh: with stale tables at call time the
+// step takes the wave sweeps, which are valid in every replay.)
+bool step_reads_eval_tables(const wf_model* m, int64_t B) { return tile_sample_capable_at(m, B) || grad_tile_capable_at(m, B); }
+// What wf_vqmc_train_step and its local half require of a model: the second-order gradient, the wave sweeps, and a sampler for B walkers (the staged
+// one beyond kWaveSampleMax).  current = false: capability, for size queries (a size queried while the tables are stale holds after the next
+// full refresh as well); true: the state at call time.
+bool vqmc_step_covered(const wf_model* m, int64_t B, bool current) {
+    return grad_supported(m, true) && m->wave_ok && (B <= kWaveSampleMax || (current ? tile_sample_ok(m, B) : tile_sample_capable_at(m, B)));
+}
 
 // presort: the rows of x arrive in any order -- evaluate on the ascending sort of each row, psi (mode 1) times (-1)^inversions (helpers.py:55-58).
 // The MFMA kernel sorts in registers; the wave and the scalar kernel read sorted rows from the model's scratch (one small launch in front,
@@ -147,8 +167,8 @@ static int dispatch(const wf_model* m, int mode, const float* x, int64_t B, floa
 }
 
 // in passes of what the workspace holds; a walker's stream is keyed by its index in the batch, whatever the passes
-int run_tile_sample(const wf_model* m, int draw, uint64_t seed, const float* u_dev, int64_t B, float* x_dev, float* latent_dev, int exact,
-                    const unsigned long long* counter_dev, float* ws, int64_t ws_floats, void* stream) {
+static int run_tile_sample(const wf_model* m, int draw, uint64_t seed, const float* u_dev, int64_t B, float* x_dev, float* latent_dev, int exact,
+                           const unsigned long long* counter_dev, float* ws, int64_t ws_floats, void* stream) {
     int64_t chunk = B;
     while (chunk > 32 && tile_sample_floats(chunk, m->mdev.nbk) > ws_floats) chunk = ((chunk / 2) + 31) / 32 * 32;
     if (tile_sample_floats(chunk, m->mdev.nbk) > ws_floats) return WF_ERR_INVALID;
@@ -161,24 +181,50 @@ int run_tile_sample(const wf_model* m, int draw, uint64_t seed, const float* u_d
     return WF_OK;
 }
 
-
-// workspace of the reverse pass per walker: tape + tails of its samples, plus 4 floats (H psi, psi, w_psi, w_lap)
-static int64_t vjp_bytes_per_walker(const wf_model* m, bool second_order) {
-    const int D = m->desc.n_dim;
-    const int kind = second_order ? m->ring2 : 0;
-    const int64_t samples = ring_samples(D, kind), nc = ring_coefs(D, kind);
-    const int64_t zrows = m->z_rows;   // gated heads: one zero_params adjoint per (sample, head lane)
-    return (samples * ((int64_t)m->nets.size() * grad_ws_rows(D, m->nbp) * nc + zrows) + wave_tail_floats(D, kind) + 4) * (int64_t)sizeof(float);
+// The walkers of one training step, stream advanced by the device counter: the staged matrix-core sampler where it applies right now (in passes
+// of what `scratch` holds), the wave sampler otherwise -- the step's coverage check has made sure that one of them takes B walkers.  (wf_sample
+// and wf_inverse_fwd choose for themselves: sample_or_invert.)
+int sample_step_walkers(const wf_model* m, uint64_t seed, const unsigned long long* counter_dev, int64_t B, float* x_dev, int exact, void* scratch,
+                        int64_t scratch_bytes, void* stream) {
+    if (tile_sample_ok(m, B)) return run_tile_sample(m, 1, seed, nullptr, B, x_dev, nullptr, exact, counter_dev, (float*)scratch, scratch_bytes / 4, stream);
+    return launch_wave_sample(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, 1, (unsigned long long)seed, nullptr, B, x_dev, nullptr, exact,
+                              counter_dev, stream);
+}
+// what the staged sampler asks of a step's workspace (0 where it does not apply): a pass of at most kTileSampleChunk walkers
+int64_t step_sampler_bytes(const wf_model* m, int64_t B) {
+    return tile_sample_capable_at(m, B) ? tile_sample_floats(std::min(B, kTileSampleChunk), m->mdev.nbk) * 4 : 0;
 }
 
+// Workspace of the taped sweeps for a chunk of walkers, in floats: the tape at 0, then the tails, four floats per walker (H psi, psi, w_psi, w_lap:
+// [4][chunk]) and, for gated heads, one zero_params adjoint per (sample, head lane) ([chunk * samples][z_rows]).  Every part is linear in the chunk.
+struct SweepWs {
+    int kind;                                          // coefficient ring of the sweep
+    int64_t samples, tails, per_walker, zws, floats;   // samples per walker; float offsets of the parts behind the tape; the total
+};
+static SweepWs sweep_ws(const wf_model* m, bool second_order, int64_t chunk) {
+    const int D = m->desc.n_dim;
+    SweepWs w{};
+    w.kind = second_order ? m->ring2 : 0;
+    w.samples = ring_samples(D, w.kind);
+    w.tails = chunk * w.samples * (int64_t)m->nets.size() * grad_ws_rows(D, m->nbp) * ring_coefs(D, w.kind);
+    w.per_walker = w.tails + chunk * wave_tail_floats(D, w.kind);
+    w.zws = w.per_walker + 4 * chunk;
+    w.floats = w.zws + chunk * w.samples * m->z_rows;
+    return w;
+}
+static int64_t vjp_bytes_per_walker(const wf_model* m, bool second_order) { return sweep_ws(m, second_order, 1).floats * (int64_t)sizeof(float); }
 
-int64_t vjp_ws_bytes(const wf_model* m, int64_t B, bool second_order) {
+// the tape of up to 32768 walkers: the wave path of every gradient and Jacobian workspace query (the Jacobian entries never take another)
+static int64_t tape_ws_bytes(const wf_model* m, int64_t B, bool second_order) {
     if (!m || B < 0) return WF_ERR_INVALID;
-    if (!m->d_grad_map || (second_order && !m->grad_psi_ok)) return WF_ERR_UNSUPPORTED;
-    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(B, 1), 32768);
-    int64_t bytes = chunk * vjp_bytes_per_walker(m, second_order);
-    if (second_order && grad_tile_capable_at(m, B)) {   // the matrix-core gradient path has a fixed part (the partial gradient blocks of every net): only where the path applies (a smaller WF_GRAD_TILE_MIN at query time moves it)
+    if (!grad_supported(m, second_order)) return WF_ERR_UNSUPPORTED;
+    return std::min<int64_t>(std::max<int64_t>(B, 1), 32768) * vjp_bytes_per_walker(m, second_order);
+}
+int64_t vjp_ws_bytes(const wf_model* m, int64_t B, bool second_order) {
+    int64_t bytes = tape_ws_bytes(m, B, second_order);
+    if (bytes > 0 && second_order && grad_tile_capable_at(m, B)) {   // the matrix-core gradient path has a fixed part (the partial gradient blocks of every net): only where the path applies (a smaller WF_GRAD_TILE_MIN at query time moves it)
         const int n_nets = (int)m->nets.size();
+        const int64_t chunk = std::min<int64_t>(std::max<int64_t>(B, 1), 32768);
         bytes = std::max<int64_t>(bytes, (energy_vjp_fixed_floats(n_nets, m->mdev.nbk) + ((chunk + 31) / 32 * 32) * energy_vjp_floats_per_walker(n_nets)) * (int64_t)sizeof(float));
     }
     return bytes;
@@ -198,12 +244,9 @@ int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* 
     const int n_nets = (int)m->nets.size();
     const int64_t fwd = plain_fwd_floats(D, m->nbp);
     const int64_t n_img = fwd * n_nets;
-    const int kind = second_order ? m->ring2 : 0;
-    const int64_t samples_per = ring_samples(D, kind), nc = ring_coefs(D, kind);
+    const SweepWs w = sweep_ws(m, second_order, chunk);
     float* tape = (float*)workspace_dev;
-    float* tails = tape + chunk * samples_per * n_nets * grad_ws_rows(D, m->nbp) * nc;
-    float* per_walker = tails + chunk * wave_tail_floats(D, kind);   // [4][chunk]
-    float* zws = m->z_rows ? per_walker + 4 * chunk : nullptr;        // [chunk * samples_per][z_rows]
+    float *tails = tape + w.tails, *per_walker = tape + w.per_walker, *zws = m->z_rows ? tape + w.zws : nullptr;
     if (B == 0) {   // the gradient of an empty batch is zero
         WF_HIP(hipMemsetAsync(grad_dev, 0, (size_t)m->n_params * sizeof(float), s));
         return WF_OK;
@@ -242,13 +285,13 @@ int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* 
         const int64_t bc = std::min(chunk, B - c0);
         const float* x = x_dev + c0 * D;
         float *wp = per_walker + 2 * chunk, *wl = per_walker + 3 * chunk;
-        int rc = launch_wave_fwd(m->dev, m->d_dev, kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x, bc, tape, tails, 1, stream);
+        int rc = launch_wave_fwd(m->dev, m->d_dev, w.kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x, bc, tape, tails, 1, stream);
         if (rc) return rc;
         const float *cw1 = w1 ? w1 + c0 : nullptr, *cw2 = w2 ? w2 + c0 : nullptr;
         if (mode == 2) {
             // (writing E_L and the weights from inside the forward kernel -- possible in RF, where a sample is a whole walker -- was
             // measured slower: the kernel grows by more than the 4.6 us launch it saves)
-            rc = launch_energy_seeds(D, kind, tails, x, bc, m->dev.constrained_mask, *pr, running_average, running_average_dev, inv_count,
+            rc = launch_energy_seeds(D, w.kind, tails, x, bc, m->dev.constrained_mask, *pr, running_average, running_average_dev, inv_count,
                                      e_loc_dev + c0, wp, wl, stream);
             if (rc) return rc;
             cw1 = wp;
@@ -259,14 +302,14 @@ int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* 
             if (rc) return rc;
             cw1 = wp;
         }
-        rc = launch_wave_bwd(m->dev, m->d_dev, (mode == 0 || mode == 3) ? 0 : 1, kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, bc, cw1, cw2, tape,
+        rc = launch_wave_bwd(m->dev, m->d_dev, (mode == 0 || mode == 3) ? 0 : 1, w.kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, bc, cw1, cw2, tape,
                              tails, zws, stream);
         if (rc) return rc;
         if (zws) {
-            rc = launch_zgrad_reduce(zws, bc * samples_per, m->z_rows, c0 > 0, m->d_zpart, m->d_zgrad, stream);
+            rc = launch_zgrad_reduce(zws, bc * w.samples, m->z_rows, c0 > 0, m->d_zpart, m->d_zgrad, stream);
             if (rc) return rc;
         }
-        rc = launch_wgrad(D, m->nbp, kind, n_nets, bc * samples_per, tape, m->d_grad_partial, c0 > 0, m->d_grad_img, fwd,
+        rc = launch_wgrad(D, m->nbp, w.kind, n_nets, bc * w.samples, tape, m->d_grad_partial, c0 > 0, m->d_grad_img, fwd,
                           single ? &split : nullptr, stream);
         if (rc) return rc;
     }
@@ -292,19 +335,16 @@ static int run_jac_chunks(const wf_model* m, int mode, const float* x_dev, int64
     DeviceGuard g(m->device);
     if (B == 0) return WF_OK;
     const int n_nets = (int)m->nets.size();
-    const int kind = second_order ? m->ring2 : 0;
-    const int64_t samples_per = ring_samples(D, kind), nc = ring_coefs(D, kind);
+    const SweepWs w = sweep_ws(m, second_order, chunk);
     float* tape = (float*)workspace_dev;
-    float* tails = tape + chunk * samples_per * n_nets * grad_ws_rows(D, m->nbp) * nc;
-    float* per_walker = tails + chunk * wave_tail_floats(D, kind);   // [4][chunk]
-    float* zws = m->z_rows ? per_walker + 4 * chunk : nullptr;        // [chunk * samples_per][z_rows]
+    float *tails = tape + w.tails, *per_walker = tape + w.per_walker, *zws = m->z_rows ? tape + w.zws : nullptr;
     // the flat parameters of each net (leaf order: the nets follow each other and cover the vector)
     std::vector<int> seg((size_t)n_nets + 1);
     for (int n = 0; n < n_nets; ++n) seg[(size_t)n] = n == 0 ? 0 : (int)m->nets[(size_t)n].offset;
     seg[(size_t)n_nets] = (int)m->n_params;
     for (int64_t c0 = 0; c0 < B; c0 += chunk) {
         const int64_t bc = std::min(chunk, B - c0);
-        int rc = launch_wave_fwd(m->dev, m->d_dev, kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x_dev + c0 * D, bc, tape, tails, 1, stream);
+        int rc = launch_wave_fwd(m->dev, m->d_dev, w.kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, x_dev + c0 * D, bc, tape, tails, 1, stream);
         if (rc) return rc;
         const float *cw1 = w1 ? w1 + c0 : nullptr, *cw2 = w2 ? w2 + c0 : nullptr;
         if (mode == 0) {   // log_pdf values (to the caller, or to a per-walker slot nobody reads) + the constant seed 1
@@ -313,32 +353,18 @@ static int run_jac_chunks(const wf_model* m, int mode, const float* x_dev, int64
             if (rc) return rc;
             cw1 = wp;
         }
-        rc = launch_wave_bwd(m->dev, m->d_dev, mode, kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, bc, cw1, cw2, tape, tails, zws, stream);
+        rc = launch_wave_bwd(m->dev, m->d_dev, mode, w.kind, m->d_tabI4, m->d_tabP3, m->d_grad_fk, bc, cw1, cw2, tape, tails, zws, stream);
         if (rc) return rc;
-        rc = launch_wjac(D, m->nbp, kind, n_nets, bc, tape, seg.data(), plain_fwd_floats(D, m->nbp), m->d_grad_map, zws ? m->d_zinv : nullptr, zws,
+        rc = launch_wjac(D, m->nbp, w.kind, n_nets, bc, tape, seg.data(), plain_fwd_floats(D, m->nbp), m->d_grad_map, zws ? m->d_zinv : nullptr, zws,
                          m->z_rows, m->d_zraw_off, m->d_plain, m->n_params, jac_dev + c0 * m->n_params, stream);
         if (rc) return rc;
     }
     return WF_OK;
 }
-// the tape of up to 32768 walkers, as the wave path of vjp_ws_bytes (no matrix-core term: these entries never take that path)
-static int64_t jac_ws_bytes(const wf_model* m, int64_t B, bool second_order) {
-    if (!m || B < 0) return WF_ERR_INVALID;
-    if (!m->d_grad_map || (second_order && !m->grad_psi_ok)) return WF_ERR_UNSUPPORTED;
-    return std::min<int64_t>(std::max<int64_t>(B, 1), 32768) * vjp_bytes_per_walker(m, second_order);
-}
 
 }  // namespace wf
 
 using namespace wf;
-
-// What wf_hamiltonian_fwd and wf_psi_coord_derivs refuse beyond check_fwd, in this order
-static int check_energy_model(const wf_model* m) {
-    if (m->desc.prior_kind != WF_PRIOR_WAVEFLOW) return WF_ERR_INVALID;
-    if (!m->wave_ok || !m->d_tabP3 || !m->d_grad_fk) return WF_ERR_UNSUPPORTED;
-    if (m->desc.n_flow_layers > 0 && m->desc.layer_kind != WF_LAYER_IMADE) return WF_ERR_UNSUPPORTED;
-    return WF_OK;
-}
 
 // The three paths of the local energy, shared by every entry point that runs its kernels: one set of predicates, switch points and chunk sizes.
 // tile / dir / wave(c0, bc, ws) launch walkers [c0, c0 + bc) with the exchange buffer ws (tile: null = the one-launch form, the whole batch);
@@ -434,6 +460,23 @@ int wf_layer_fwd(const wf_model* m, int layer, const float* u_in_dev, int64_t B,
     return launch_scalar_layer(m->dev, m->d_dev, layer, u_in_dev, B, y_dev, logdet_dev, bin_idx_dev, stream);
 }
 
+// wf_sample (draw: from `seed`) and wf_inverse_fwd (of u_dev) behind their coupling-stack branches, any batch size: the staged sampler in the
+// model's scratch where it applies, one wave per walker up to WF_WAVE_SAMPLE_MAX walkers (read per call), one lane per walker otherwise.
+static int sample_or_invert(const wf_model* m, int draw, uint64_t seed, const float* u_dev, int64_t B, float* x_dev, float* latent_dev, int exact,
+                            void* stream) {
+    if (tile_sample_ok(m, B)) {
+        const int64_t fl = tile_sample_floats(std::min(B, kTileSampleChunk), m->mdev.nbk);
+        int rc = ensure_scratch(m, fl);
+        if (rc) return rc;
+        return run_tile_sample(m, draw, seed, u_dev, B, x_dev, latent_dev, exact, nullptr, m->d_scratch, fl, stream);
+    }
+    if (m->wave_ok && B <= env_wave_sample_max())
+        return launch_wave_sample(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, draw, (unsigned long long)seed, u_dev, B, x_dev, latent_dev,
+                                  exact, nullptr, stream);
+    return draw ? launch_scalar_sample(m->dev, m->d_dev, (unsigned long long)seed, B, x_dev, latent_dev, exact, stream)
+                : launch_scalar_inverse(m->dev, m->d_dev, u_dev, B, x_dev, exact, stream);
+}
+
 int wf_inverse_fwd(const wf_model* m, const float* u_dev, int64_t B, float* x_dev, int32_t exact, void* stream) {
     int rc = check_fwd(m, u_dev, B, x_dev);
     if (rc) return rc;
@@ -444,15 +487,7 @@ int wf_inverse_fwd(const wf_model* m, const float* u_dev, int64_t B, float* x_de
         if (rc) return rc;
         return launch_nsc_model(m->nsc, 3, u_dev, B, m->d_scratch, x_dev, stream);
     }
-    if (tile_sample_ok(m, B)) {
-        const int64_t fl = tile_sample_floats(std::min(B, kTileSampleChunk), m->mdev.nbk);
-        rc = ensure_scratch(m, fl);
-        if (rc) return rc;
-        return run_tile_sample(m, 0, 0, u_dev, B, x_dev, nullptr, exact, nullptr, m->d_scratch, fl, stream);
-    }
-    if (m->wave_ok && B <= env_wave_sample_max())
-        return launch_wave_sample(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, 0, 0ull, u_dev, B, x_dev, nullptr, exact, nullptr, stream);
-    return launch_scalar_inverse(m->dev, m->d_dev, u_dev, B, x_dev, exact, stream);
+    return sample_or_invert(m, 0, 0, u_dev, B, x_dev, nullptr, exact, stream);
 }
 
 int wf_sample(const wf_model* m, uint64_t seed, int64_t B, float* x_dev, float* latent_dev, int32_t exact, void* stream) {
@@ -468,16 +503,7 @@ int wf_sample(const wf_model* m, uint64_t seed, int64_t B, float* x_dev, float* 
         if (rc) return rc;
         return launch_nsc_model(m->nsc, 3, z, B, m->d_scratch, x_dev, stream);
     }
-    if (tile_sample_ok(m, B)) {
-        const int64_t fl = tile_sample_floats(std::min(B, kTileSampleChunk), m->mdev.nbk);
-        rc = ensure_scratch(m, fl);
-        if (rc) return rc;
-        return run_tile_sample(m, 1, seed, nullptr, B, x_dev, latent_dev, exact, nullptr, m->d_scratch, fl, stream);
-    }
-    if (m->wave_ok && B <= env_wave_sample_max())
-        return launch_wave_sample(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, 1, (unsigned long long)seed, nullptr, B, x_dev, latent_dev,
-                                  exact, nullptr, stream);
-    return launch_scalar_sample(m->dev, m->d_dev, (unsigned long long)seed, B, x_dev, latent_dev, exact, stream);
+    return sample_or_invert(m, 1, seed, nullptr, B, x_dev, latent_dev, exact, stream);
 }
 
 int wf_hamiltonian_fwd(const wf_model* m, const float* x_dev, int64_t B, const float* protons_host, int32_t n_protons, float* hpsi_dev,
@@ -552,8 +578,8 @@ int wf_logpdf_vjp(const wf_model* m, const float* x_dev, int64_t B, const float*
     return run_vjp_chunks(m, 0, false, x_dev, B, w_dev, nullptr, nullptr, 0.0f, 0.0f, nullptr, grad_dev, workspace_dev, workspace_bytes, stream);
 }
 
-int64_t wf_psi_jac_workspace_bytes(const wf_model* m, int64_t B) { return jac_ws_bytes(m, B, true); }
-int64_t wf_logpdf_jac_workspace_bytes(const wf_model* m, int64_t B) { return jac_ws_bytes(m, B, false); }
+int64_t wf_psi_jac_workspace_bytes(const wf_model* m, int64_t B) { return tape_ws_bytes(m, B, true); }
+int64_t wf_logpdf_jac_workspace_bytes(const wf_model* m, int64_t B) { return tape_ws_bytes(m, B, false); }
 
 int wf_psi_jac(const wf_model* m, const float* x_dev, int64_t B, const float* w_psi_dev, const float* w_lap_dev, float* jac_dev, void* workspace_dev,
                int64_t workspace_bytes, void* stream) {

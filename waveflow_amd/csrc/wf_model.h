@@ -1,4 +1,4 @@
-// wf_model.h -- private header of the host units (wf_runtime.cpp, wf_model_build.cpp, wf_model_images.cpp, wf_dispatch.cpp, wf_train.cpp):
+// wf_model.h -- private header of the host units (wf_runtime.cpp, wf_model_build.cpp, wf_model_images.cpp, wf_dispatch.cpp, wf_train.cpp, wf_train_sr.cpp):
 // struct wf_model and the few helpers those units share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "wf_internal.h"
+#include "wf_layout.h"
 
 #define WF_HIP(call)                                   \
     do {                                               \
@@ -161,11 +162,13 @@ bool f16_overflow(const wf_model* cm);
 
 // ---- wf_dispatch.cpp: path predicates and chunk loops the training steps share with the entry points
 bool make_protons(const float* host, int n, Protons* out);
-bool tile_sample_capable_at(const wf_model* m, int64_t B);
-bool tile_sample_ok(const wf_model* m, int64_t B);
-bool grad_tile_capable_at(const wf_model* m, int64_t B);
-int run_tile_sample(const wf_model* m, int draw, uint64_t seed, const float* u_dev, int64_t B, float* x_dev, float* latent_dev, int exact,
-                    const unsigned long long* counter_dev, float* ws, int64_t ws_floats, void* stream);
+bool grad_supported(const wf_model* m, bool second_order);
+int check_energy_model(const wf_model* m);
+bool step_reads_eval_tables(const wf_model* m, int64_t B);
+bool vqmc_step_covered(const wf_model* m, int64_t B, bool current);
+int sample_step_walkers(const wf_model* m, uint64_t seed, const unsigned long long* counter_dev, int64_t B, float* x_dev, int exact, void* scratch,
+                        int64_t scratch_bytes, void* stream);
+int64_t step_sampler_bytes(const wf_model* m, int64_t B);
 int64_t vjp_ws_bytes(const wf_model* m, int64_t B, bool second_order);
 int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* x_dev, int64_t B, const float* w1, const float* w2,
                    const Protons* pr, float running_average, float inv_count, float* e_loc_dev, float* grad_dev, void* workspace_dev,

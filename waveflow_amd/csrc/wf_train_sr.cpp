@@ -14,13 +14,8 @@ namespace {
 
 constexpr int64_t kSrStepMaxBatch = 4096;   // wf_sr_solve
 
-int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
-// the models the step covers: those of wf_psi_jac (check_grad, second order), of wf_vqmc_train_step, and of the wave sweep of wf_hamiltonian_fwd
-bool model_covered(const wf_model* m) {
-    return m->d_grad_map && m->grad_psi_ok && m->wave_ok && m->desc.prior_kind == WF_PRIOR_WAVEFLOW && m->d_tabP3 && m->d_grad_fk &&
-           !(m->desc.n_flow_layers > 0 && m->desc.layer_kind != WF_LAYER_IMADE);
-}
+// the models the step covers: those of wf_psi_jac (second-order gradients) that wf_hamiltonian_fwd accepts, wave sweeps and sampler with them
+bool model_covered(const wf_model* m) { return grad_supported(m, true) && check_energy_model(m) == WF_OK; }
 
 // What follows the fixed-size vectors in the workspace, in this order: rows, the batch x batch matrix, the workspace of waveflow_sr.h, and one
 // area the sampler (staged form only), the energy sweep and the tape of wf_psi_jac use one after the other.
@@ -34,31 +29,25 @@ Layout layout_of(const wf_model* m, int64_t batch) {
     const int D = m->desc.n_dim;
     const int64_t P = m->n_params;
     Layout l{};
-    int64_t p = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t at = p;
-        p += align256(bytes);
-        return at;
-    };
-    l.x = take(batch * D * 4);
-    l.hpsi = take(batch * 4);
-    l.psi = take(batch * 4);
-    l.e_loc = take(batch * 4);
-    l.inv = take(batch * 4);
-    l.rhs = take(batch * 8);
-    l.y = take(batch * 8);
-    l.d = take(P * 4);
-    l.scalars = take(256);   // block sums [3] doubles at 0, the solver's info at 64, the verdict's flag at 68
-    l.sums_ws = take(block_sums_ws_bytes(batch));
-    l.rows = take(batch * P * 4);
-    l.t = take(batch * batch * 8);
+    Bump b;
+    l.x = b.take(batch * D * 4);
+    l.hpsi = b.take(batch * 4);
+    l.psi = b.take(batch * 4);
+    l.e_loc = b.take(batch * 4);
+    l.inv = b.take(batch * 4);
+    l.rhs = b.take(batch * 8);
+    l.y = b.take(batch * 8);
+    l.d = b.take(P * 4);
+    l.scalars = b.take(256);   // block sums [3] doubles at 0, the solver's info at 64, the verdict's flag at 68
+    l.sums_ws = b.take(block_sums_ws_bytes(batch));
+    l.rows = b.take(batch * P * 4);
+    l.t = b.take(batch * batch * 8);
     l.sr_bytes = align256(wf_sr_workspace_bytes(batch, P));
-    l.sr = take(l.sr_bytes);
+    l.sr = b.take(l.sr_bytes);
     const int64_t energy = batch * std::max(wave_tail_floats(D, 1), wave_tail_floats(D, 3)) * 4;
-    const int64_t sampler = tile_sample_capable_at(m, batch) ? tile_sample_floats(std::min(batch, kTileSampleChunk), m->mdev.nbk) * 4 : 0;
-    l.tape_bytes = align256(std::max(wf_psi_jac_workspace_bytes(m, batch), std::max(energy, sampler)));
-    l.tape = take(l.tape_bytes);
-    l.total = p;
+    l.tape_bytes = align256(std::max(wf_psi_jac_workspace_bytes(m, batch), std::max(energy, step_sampler_bytes(m, batch))));
+    l.tape = b.take(l.tape_bytes);
+    l.total = b.at;
     return l;
 }
 
@@ -98,10 +87,7 @@ int wf_vqmc_sr_step(wf_model* m, const wf_sr_train_state* st, uint64_t seed, int
     int rc = WF_OK;
     // walkers ~ the sampler of wf_vqmc_train_step at this batch size, stream advanced by the device counter
     if (draw) {
-        rc = tile_sample_ok(m, batch)
-                 ? run_tile_sample(m, 1, seed, nullptr, batch, x, nullptr, exact_sampler, counter, (float*)tape, l.tape_bytes / 4, stream)
-                 : launch_wave_sample(m->dev, m->d_dev, m->d_tabI4, m->d_tabP3, m->d_grad_fk, 1, (unsigned long long)seed, nullptr, batch, x, nullptr,
-                                      exact_sampler, counter, stream);
+        rc = sample_step_walkers(m, seed, counter, batch, x, exact_sampler, tape, l.tape_bytes, stream);
         if (rc) return rc;
     }
     // H psi and psi: the wave sweep of wf_hamiltonian_fwd with its tails in the workspace; local energies and the centred right-hand side
@@ -123,8 +109,7 @@ int wf_vqmc_sr_step(wf_model* m, const wf_sr_train_state* st, uint64_t seed, int
     if (rc) return rc;
     rc = launch_sr_update(st->params_dev, d, P, st->step_size_dev, flag, stream);
     if (rc) return rc;
-    // (the refresh rule of wf_vqmc_train_step: a step at a batch size of the staged sampler replays on fresh tables whatever the deferral says)
-    rc = apply_params(m, st->params_dev, stream, !st->defer_eval_tables || tile_sample_capable_at(m, batch) || grad_tile_capable_at(m, batch));
+    rc = apply_params(m, st->params_dev, stream, !st->defer_eval_tables || step_reads_eval_tables(m, batch));
     if (rc) return rc;
     // batch sums of the local energies -> loss ring, step counter + 1
     return launch_block_sums(e_loc, batch, sums, sums_ws, block_sums_ws_bytes(batch), stream, st->loss_ring_dev, st->ring_len, counter);

@@ -12,6 +12,7 @@ with m_hat = m / (1 - b1^(i+1)), v_hat = v / (1 - b2^(i+1)) for the step index i
 import json
 import os
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -34,13 +35,15 @@ class OptState:
         return self.model is not None
 
 
+def _lr_at(step_size, i):
+    """The step size of step i: a number, or a schedule called with i."""
+    return float(step_size(i) if callable(step_size) else step_size)
+
+
 def adam(step_size, b1=0.9, b2=0.999, eps=1e-8, model=None):
     """-> (opt_init, opt_update, get_params), the triple protocol of jax.example_libraries.optimizers.
     With `model` (a DeviceModel) the state lives on that model's GPU, opt_update runs wf_adam_step in place and get_params
     returns core.DeviceParams; otherwise everything is numpy on the host."""
-    def lr_at(i):
-        return float(step_size(i) if callable(step_size) else step_size)
-
     def opt_init(params):
         x = flatten_params(params).astype(np.float32)
         if model is None:
@@ -56,7 +59,7 @@ def adam(step_size, b1=0.9, b2=0.999, eps=1e-8, model=None):
             import torch
             g = grads if hasattr(grads, "is_cuda") else torch.as_tensor(flatten_params(grads) if not isinstance(grads, np.ndarray) else grads)
             g = g.to(state.x.device, dtype=torch.float32).contiguous()
-            state.model.adam_step(state.x, g, state.m, state.v, i, lr_at(i), b1, b2, eps)
+            state.model.adam_step(state.x, g, state.m, state.v, i, _lr_at(step_size, i), b1, b2, eps)
             state.version += 1
             return state
         g = grads if isinstance(grads, np.ndarray) and grads.ndim == 1 else flatten_params(grads)
@@ -66,7 +69,7 @@ def adam(step_size, b1=0.9, b2=0.999, eps=1e-8, model=None):
         v = (one - np.float32(b2)) * np.square(g) + np.float32(b2) * state.v
         mhat = m / (one - np.float32(b1) ** np.float32(i + 1))
         vhat = v / (one - np.float32(b2) ** np.float32(i + 1))
-        x = state.x - np.float32(lr_at(i)) * mhat / (np.sqrt(vhat) + np.float32(eps))
+        x = state.x - np.float32(_lr_at(step_size, i)) * mhat / (np.sqrt(vhat) + np.float32(eps))
         return OptState(state.template, x.astype(np.float32), m, v)
 
     def get_params(state):
@@ -273,7 +276,7 @@ def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **
     learning_rate: a number, or a schedule called with `epoch`) -> (new params, loss).  `params` is left as it is: the result is a new
     pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one."""
     d, loss_val = sr_natural_gradient(params, psi, h_fn, batch, group=group, **damping)
-    lr = float(learning_rate(epoch) if callable(learning_rate) else learning_rate)
+    lr = _lr_at(learning_rate, epoch)
     if isinstance(params, DeviceParams):
         return DeviceParams(params.template, params.flat - lr * d.to(params.flat.device), params.version + 1), loss_val
     flat = flatten_params(params).astype(np.float32)
@@ -305,6 +308,88 @@ def _load_optimizer_state(save_dir, opt_state, epoch):
     else:
         opt_state.m, opt_state.v = m, v
     return True
+
+
+def capture_step(model, step, warm_up=None, error=None):
+    """`step` (library calls on resident data, workspaces allocated beforehand) captured once in a hipGraph on a side stream -> the callable
+    that replays it.  warm_up() runs on that stream first, outside the capture: what must have happened once before the sequence is recorded,
+    with whatever undoes its effects.  A failed capture leaves the side stream in an undefined capture state, so there is no fallback to
+    call-by-call: RuntimeError(error) from the cause (error=None: the cause as it is)."""
+    import torch
+    side = torch.cuda.Stream(device=model.device)
+    side.wait_stream(torch.cuda.current_stream(model.device))
+    try:
+        with torch.cuda.stream(side):
+            if warm_up is not None:
+                warm_up()
+            side.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                step()
+    except Exception as e:
+        if error is None:
+            raise
+        raise RuntimeError(error) from e
+    torch.cuda.current_stream(model.device).wait_stream(side)
+    return graph.replay
+
+
+def loss_ring_reader(model, st, first, sign=1.0, after=None):
+    """-> fetch(upto): the losses (sign * sum / count of a ring slot) of the steps after the last one fetched -- at first those from `first` on --
+    up to step `upto`, read from the train state's loss ring once the device has caught up.  The caller fetches at least every ring_len steps.
+    after(upto), if given, runs behind every read (what else the host looks at while the device is idle)."""
+    import torch
+    fetched = [first - 1]   # losses of the steps up to here are on the host
+    n = st["ring_len"]
+
+    def fetch(upto):
+        torch.cuda.synchronize(model.device)
+        ring = st["ring"].cpu().numpy()
+        new = [float(sign * ring[e % n, 0] / ring[e % n, 2]) for e in range(fetched[0] + 1, upto + 1)]
+        fetched[0] = upto
+        if after is not None:
+            after(upto)
+        return new
+    return fetch
+
+
+def run_device_loop(model, opt_state, get_params, replay, fetch, record, first, last, checkpoint_every, checkpoint, fetch_every, fetched,
+                    report_every=0):
+    """Epochs first .. last of a step that runs on the device without the host (`replay`: one graph launch or a few library calls; losses in a
+    ring, read by `fetch`) -> the final parameters.  An epoch without a boundary costs the host its modulo tests and one call of `replay`.
+    checkpoint(epoch, params): before epoch 1 and every checkpoint_every-th epoch, on the parameters after epoch - 1, the losses up to there
+    recorded (record(new) appends them to the caller's lists); the model's images are refreshed behind it.  fetched(epoch, new): after every
+    fetch_every-th (and report_every-th, if set) epoch, with the losses since the last fetch, which it records itself.  At the end every loss
+    is recorded and every image of the model, evaluation tables included, holds the final parameters."""
+    for epoch in range(first, last + 1):
+        if epoch % checkpoint_every == 0 or epoch == 1:
+            record(fetch(epoch - 1))
+            opt_state.version += 1
+            checkpoint(epoch, get_params(opt_state))
+            model.set_params_device(opt_state.x)
+        replay()
+        if epoch % fetch_every == 0 or (report_every and epoch % report_every == 0):
+            fetched(epoch, fetch(epoch))
+    record(fetch(last))
+    opt_state.version += 1
+    model.set_params_device(opt_state.x)
+    return get_params(opt_state)
+
+
+class _Run(SimpleNamespace):
+    """What every loop of start_training works on: the model's closures, the optimiser state, `loss` and `energies` (which grow in place), the
+    host generator, rank and group."""
+
+    def record(self, new):
+        self.loss.extend(new)
+        self.energies.extend([[v] for v in new])
+
+    def checkpoint(self, seed, epoch, params, save_optimizer):
+        """The reference's artefacts, and Adam's moments next to them, from rank 0 (every rank draws `seed`: the host streams stay aligned)."""
+        if self.rank == 0:
+            helpers.create_checkpoint_wavefunc(seed, self.save_dir, self.psi, self.sample, params, epoch, self.loss, self.energies, self.system_dict)
+            if save_optimizer:
+                _save_optimizer_state(self.save_dir, self.opt_state, epoch)
 
 
 class ModelTrainer:
@@ -373,8 +458,6 @@ class ModelTrainer:
                 warnings.warn(f"{save_dir}/optimizer_state.npz does not match checkpoint epoch {start_epoch}: Adam moments restart from zero")
             loss = np.load(f'{save_dir}/loss.npy').tolist()
             energies = np.load(f'{save_dir}/energies.npy').tolist()
-        params = get_params(opt_state)
-        running_average = np.zeros(1)
         system_dict = {"system_name": self.system_name, "box_length": self.box_length, "n_particle": self.n_particle,
                        "n_space_dimension": self.n_space_dimension, "window": self.window, "n_plotting": self.n_plotting}
         if rank == 0:
@@ -383,157 +466,128 @@ class ModelTrainer:
                 json.dump(system_dict, fout_sys, indent=4)
         if verbose:
             print("Start training...")
+        run = _Run(psi=psi, sample=sample, h_fn=h_fn, opt_state=opt_state, opt_update=opt_update, get_params=get_params, start_epoch=start_epoch,
+                   loss=loss, energies=energies, system_dict=system_dict, save_dir=save_dir, rng=rng, verbose=verbose,
+                   group=group if distributed else None, rank=rank, local_batch=local_batch)
         # the whole step as one captured launch sequence, where the library has it (models the sweeps cover; the wave sampler: <= 131072 walkers
-        # per step, no such limit where the staged large-batch sampler applies); otherwise the host-stepped loop below (sampler, loss + gradient, Adam: three library calls per step)
+        # per step, no such limit where the staged large-batch sampler applies); otherwise the host-stepped loop (sampler, loss + gradient, Adam: three library calls per step)
         # Sharded over several processes: the same sequence in two halves around the step's one all-reduce.
-        if optimizer == 'sr':
-            train = self._train_sr_device if getattr(self, "sr_on_device", False) else self._train_sr
-            params = train(psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose)
-            self.params, self.loss, self.energies = params, loss, energies
-            self.psi, self.log_pdf, self.sample, self.h_fn = psi, log_pdf, sample, h_fn
-            return params, loss
-        fused = self.use_graph and local_batch >= 1
+        fused = optimizer == 'adam' and self.use_graph and local_batch >= 1
         if fused:
             from ._lib import WfError
             try:
                 fused = psi.model.train_step_workspace_bytes(local_batch) > 0
             except WfError:   # (the library has no fused step for this model or batch)
                 fused = False
-        if fused:
-            params, loss, energies = self._train_graphed(psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict,
-                                                         save_dir, rng, verbose, group=group if distributed else None, rank=rank,
-                                                         local_batch=local_batch)
-            self.params, self.loss, self.energies = params, loss, energies
-            self.psi, self.log_pdf, self.sample, self.h_fn = psi, log_pdf, sample, h_fn
-            return params, loss
-        for epoch in range(start_epoch + 1, start_epoch + self.num_epochs + 1):
-            ckpt_seed, step_seed = int(rng.integers(1 << 31)), int(rng.integers(1 << 31))   # same host stream on every rank
-            if (epoch % self.log_every == 0 or epoch == 1) and rank == 0:
-                helpers.create_checkpoint_wavefunc(ckpt_seed, save_dir, psi, sample, params, epoch, loss, energies, system_dict)
-                _save_optimizer_state(save_dir, opt_state, epoch)
-            batch = sample(step_seed + 7919 * rank, params, local_batch, exact_inverse=self.exact_sampler)
-            opt_state, new_loss = train_step_efficient(epoch, psi, h_fn, opt_update, opt_state, params, batch, running_average,
-                                                       group=group)
-            if epoch % 100 == 0:
-                running_average = np.asarray(loss[-100:]).mean()
-            if epoch % self.log_every == 0 and verbose:
-                print(f"epoch {epoch} | Loss: {round(float(new_loss), 3)}")
-            params = get_params(opt_state)
-            loss.append(new_loss)
-            energies.append([new_loss])
+        if optimizer == 'sr':
+            params = (self._train_sr_device if getattr(self, "sr_on_device", False) else self._train_sr)(run)
+        elif fused:
+            params = self._train_graphed(run)
+        else:
+            params = self._train_adam(run, group)
         self.params, self.loss, self.energies = params, loss, energies
         self.psi, self.log_pdf, self.sample, self.h_fn = psi, log_pdf, sample, h_fn
         return params, loss
 
-    def _train_sr(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose):
-        """The host-stepped loop of start_training with train_step_sr in the place of the Adam step: eager (the solver's status is read every
-        step), parameters on the device in opt_state.x, no optimiser state to save.  `loss` and `energies` grow in place."""
-        params = get_params(opt_state)
-        for epoch in range(start_epoch + 1, start_epoch + self.num_epochs + 1):
-            ckpt_seed, step_seed = int(rng.integers(1 << 31)), int(rng.integers(1 << 31))
+    def _train_host(self, run, step, save_optimizer):
+        """The host-stepped loop: per epoch two draws from the host stream (checkpoint seed, sampler seed: the same on every rank), a checkpoint
+        from rank 0 at epoch 1 and every log_every epochs, this rank's walkers, and step(epoch, params, batch) -> loss, which moves run.opt_state."""
+        params = run.get_params(run.opt_state)
+        for epoch in range(run.start_epoch + 1, run.start_epoch + self.num_epochs + 1):
+            ckpt_seed, step_seed = int(run.rng.integers(1 << 31)), int(run.rng.integers(1 << 31))
             if epoch % self.log_every == 0 or epoch == 1:
-                helpers.create_checkpoint_wavefunc(ckpt_seed, save_dir, psi, sample, params, epoch, loss, energies, system_dict)
-            batch = sample(step_seed, params, self.batch_size, exact_inverse=self.exact_sampler)
-            new_params, new_loss = train_step_sr(epoch, psi, h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}))
-            opt_state.x.copy_(new_params.flat)
-            opt_state.version += 1
-            params = get_params(opt_state)
-            if epoch % self.log_every == 0 and verbose:
+                run.checkpoint(ckpt_seed, epoch, params, save_optimizer)
+            batch = run.sample(step_seed + 7919 * run.rank, params, run.local_batch, exact_inverse=self.exact_sampler)
+            new_loss = step(epoch, params, batch)
+            params = run.get_params(run.opt_state)
+            if epoch % self.log_every == 0 and run.verbose:
                 print(f"epoch {epoch} | Loss: {round(float(new_loss), 3)}")
-            loss.append(new_loss)
-            energies.append([new_loss])
+            run.record([new_loss])
         return params
 
-    def _train_sr_device(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose):
-        """optimizer='sr' with sr_on_device: the loop of _train_graphed around wf_vqmc_sr_step.  Per epoch one graph launch (use_graph) or one
-        library call; the learning rate is a device scalar, rewritten before the step when `learning_rate` is a schedule; the host looks at the
-        loss ring every 100 epochs and at checkpoints, and at the step's status with it: steps the solver refused (a pivot that is not positive,
-        a step that is not finite) leave the parameters as they are and are reported once, with their count.  `loss` and `energies` grow in place."""
+    def _train_adam(self, run, group):
+        """The host-stepped loop with train_step_efficient (`group` as start_training received it: None means not distributed); the running
+        average follows the losses every 100 epochs, before that epoch's loss joins them (vqmc.py:112-118)."""
+        average = [np.zeros(1)]
+
+        def step(epoch, params, batch):
+            run.opt_state, new_loss = train_step_efficient(epoch, run.psi, run.h_fn, run.opt_update, run.opt_state, params, batch, average[0], group=group)
+            if epoch % 100 == 0:
+                average[0] = np.asarray(run.loss[-100:]).mean()
+            return new_loss
+        return self._train_host(run, step, save_optimizer=True)
+
+    def _train_sr(self, run):
+        """The host-stepped loop with train_step_sr in the place of the Adam step: eager (the solver's status is read every step), parameters on
+        the device in opt_state.x, no optimiser state to save."""
+        def step(epoch, params, batch):
+            new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}))
+            run.opt_state.x.copy_(new_params.flat)
+            run.opt_state.version += 1
+            return new_loss
+        return self._train_host(run, step, save_optimizer=False)
+
+    def _train_sr_device(self, run):
+        """optimizer='sr' with sr_on_device: run_device_loop around wf_vqmc_sr_step.  Per epoch one graph launch (use_graph) or one library call;
+        the learning rate is a device scalar, rewritten before the step when `learning_rate` is a schedule; the host looks at the loss ring every
+        100 epochs and at checkpoints, and at the step's status with it: steps the solver refused (a pivot that is not positive, a step that is not
+        finite) leave the parameters as they are and are reported once, with their count."""
         import warnings
-        import torch
-        model = psi.model
+        model, opt_state, start_epoch = run.psi.model, run.opt_state, run.start_epoch
         lr = self.learning_rate
-        lr_at = (lambda e: float(lr(e))) if callable(lr) else (lambda e: float(lr))
         damping = getattr(self, "sr_damping", {})
         batch = int(self.batch_size)
         st = model.make_sr_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True)
         model.set_params_device(opt_state.x)
-        seed = int(rng.integers(1 << 62))
+        seed = int(run.rng.integers(1 << 62))
 
         def step():
-            model.sr_step(st, seed, batch, h_fn.protons, exact_sampler=self.exact_sampler, **damping)
+            model.sr_step(st, seed, batch, run.h_fn.protons, exact_sampler=self.exact_sampler, **damping)
         st["ws"] = model._workspace(model.sr_step_workspace_bytes(batch), opt_state.x.device)   # allocated here, outside the capture
-        replay = step
-        if self.use_graph:
-            side = torch.cuda.Stream(device=model.device)
-            side.wait_stream(torch.cuda.current_stream(model.device))
-            try:
-                with torch.cuda.stream(side):
-                    # one step outside the capture (every kernel of the sequence has run once before it is recorded) at learning rate 0: the
-                    # parameters come out bitwise as they went in; what it left in the counter, the rings and the status is put back
-                    step()
-                    st["counter"].fill_(start_epoch + 1)
-                    for name in ("ring", "norm_ring", "status"):
-                        st[name].zero_()
-                    side.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=side):
-                        step()
-                replay = graph.replay
-            except Exception as e:
-                raise RuntimeError("hipGraph capture of the stochastic-reconfiguration step failed") from e
-            torch.cuda.current_stream(model.device).wait_stream(side)
-        fetched = [start_epoch]   # losses of the epochs up to here are on the host
+
+        def warm_up():
+            # one step outside the capture (every kernel of the sequence has run once before it is recorded) at learning rate 0: the
+            # parameters come out bitwise as they went in; what it left in the counter, the rings and the status is put back
+            step()
+            st["counter"].fill_(start_epoch + 1)
+            for name in ("ring", "norm_ring", "status"):
+                st[name].zero_()
+        launch = capture_step(model, step, warm_up, "hipGraph capture of the stochastic-reconfiguration step failed") if self.use_graph else step
+        if callable(lr):   # a schedule: the rate of its epoch in front of every step
+            epochs = iter(range(start_epoch + 1, start_epoch + self.num_epochs + 1))
+
+            def replay():
+                st["step_size"].fill_(_lr_at(lr, next(epochs)))
+                launch()
+        else:
+            st["step_size"].fill_(float(lr))
+            replay = launch
         warned = [False]
 
-        def fetch(upto):
-            torch.cuda.synchronize(model.device)
-            ring = st["ring"].cpu().numpy()
-            new = [float(ring[e % st["ring_len"], 0] / ring[e % st["ring_len"], 2]) for e in range(fetched[0] + 1, upto + 1)]
-            fetched[0] = upto
+        def status(upto):
             info, skipped = (int(v) for v in st["status"].cpu().tolist())
             if skipped and not warned[0]:
                 warned[0] = True
                 warnings.warn(f"stochastic reconfiguration: {skipped} of the first {upto - start_epoch} steps were skipped (status of the last step: "
                               f"{info}; > 0: that pivot of the shifted B x B matrix is not positive, -1: the step is not finite) -- more damping")
-            return new
 
-        params = get_params(opt_state)
-        for epoch in range(start_epoch + 1, start_epoch + self.num_epochs + 1):
-            if epoch % self.log_every == 0 or epoch == 1:
-                new = fetch(epoch - 1)
-                loss.extend(new)
-                energies.extend([[v] for v in new])
-                opt_state.version += 1
-                params = get_params(opt_state)
-                helpers.create_checkpoint_wavefunc(int(rng.integers(1 << 31)), save_dir, psi, sample, params, epoch, loss, energies, system_dict)
-                model.set_params_device(opt_state.x)
-            if callable(lr) or epoch == start_epoch + 1:
-                st["step_size"].fill_(lr_at(epoch))
-            replay()
-            if epoch % 100 == 0:
-                new = fetch(epoch)
-                loss.extend(new)
-                energies.extend([[v] for v in new])
-                if epoch % self.log_every == 0 and verbose:
-                    print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
-        new = fetch(start_epoch + self.num_epochs)
-        loss.extend(new)
-        energies.extend([[v] for v in new])
-        opt_state.version += 1
-        model.set_params_device(opt_state.x)   # every image of the model, evaluation tables included, holds the final parameters
-        return get_params(opt_state)
+        def fetched(epoch, new):
+            run.record(new)
+            if epoch % self.log_every == 0 and run.verbose:
+                print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
+        return run_device_loop(model, opt_state, run.get_params, replay, loss_ring_reader(model, st, start_epoch + 1, after=status), run.record,
+                               start_epoch + 1, start_epoch + self.num_epochs, self.log_every,
+                               lambda epoch, params: run.checkpoint(int(run.rng.integers(1 << 31)), epoch, params, False), 100, fetched)
 
-    def _train_graphed(self, psi, sample, h_fn, opt_state, get_params, start_epoch, loss, energies, system_dict, save_dir, rng, verbose,
-                       group=None, rank=0, local_batch=None):
-        """The training loop with the step captured once in a hipGraph: per epoch one graph launch; the host looks at the
+    def _train_graphed(self, run):
+        """The training loop with the step captured once in a hipGraph (run_device_loop): per epoch one graph launch; the host looks at the
         losses every 100 epochs (to refresh the running average, vqmc.py:112-113) and at checkpoints.
-        With `group` (one process per GPU) the step is wf_vqmc_train_step_local -> all-reduce of one packed fp64 buffer ->
+        With run.group (one process per GPU) the step is wf_vqmc_train_step_local -> all-reduce of one packed fp64 buffer ->
         wf_vqmc_train_step_apply, issued call by call (WF_GRAPH_COLLECTIVE=1 captures it with the RCCL collective inside) -- either
         way without a host synchronisation per step."""
         import torch
         from .distributed import _all_reduce_sum
-        model = psi.model
+        model, opt_state, start_epoch, group, rank, local_batch = run.psi.model, run.opt_state, run.start_epoch, run.group, run.rank, run.local_batch
         # (the steps leave out the tables only the large-batch evaluation kernel reads; every evaluation below goes through
         # ensure_params / set_params_device first, and the loop ends with a full refresh)
         # Large batches are the exception: from WF_GRAD_TILE_MIN walkers per step on (default 16 384) the loss + gradient of the two-particle family runs
@@ -545,79 +599,35 @@ class ModelTrainer:
         large = (tile_min > 0 and per_step >= tile_min) or (sample_min > 0 and per_step >= sample_min)
         st = model.make_train_state(opt_state.x, opt_state.m, opt_state.v, start_epoch + 1, ring_len=128, defer_eval_tables=not large)
         model.set_params_device(opt_state.x)
-        seed = int(rng.integers(1 << 62))
+        seed = int(run.rng.integers(1 << 62))
+        warm_up, capture = None, True
         if group is None:
             def step():
-                model.train_step(st, seed, self.batch_size, h_fn.protons, self.learning_rate, exact_sampler=self.exact_sampler)
-            nbytes = model.train_step_workspace_bytes(self.batch_size)
-            capture = True
+                model.train_step(st, seed, self.batch_size, run.h_fn.protons, self.learning_rate, exact_sampler=self.exact_sampler)
         else:
             import torch.distributed as dist
             red = torch.zeros(model.n_params + 3, dtype=torch.float64, device=opt_state.x.device)
 
             def step():   # every rank draws its own walkers (stream seed + 7919 rank); the tangent rule carries 1 / global batch
-                model.train_step_local(st, seed + 7919 * rank, local_batch, h_fn.protons, 1.0 / float(self.batch_size), red,
-                                       exact_sampler=self.exact_sampler)
+                model.train_step_local(st, seed + 7919 * rank, local_batch, run.h_fn.protons, 1.0 / float(self.batch_size), red, exact_sampler=self.exact_sampler)
                 _all_reduce_sum(red, group)
                 model.train_step_apply(st, red, self.learning_rate)
-            nbytes = model.train_step_workspace_bytes(local_batch)
+
+            def warm_up():   # RCCL sets up its communicator at the first collective: outside the capture
+                _all_reduce_sum(torch.zeros(8, dtype=torch.float64, device=opt_state.x.device), group)
             # Capturing the collective in the graph measured no faster than issuing the three calls (4.91 vs 4.94 s per 20 000 steps, one
             # rank) and could not be tried on several GPUs here: opt-in.
             capture = dist.get_backend(group) == "nccl" and os.environ.get("WF_GRAPH_COLLECTIVE") == "1"
-        st["ws"] = model._workspace(nbytes, opt_state.x.device)   # allocated here, outside the capture
-        replay = step
-        if capture:
-            side = torch.cuda.Stream(device=model.device)
-            side.wait_stream(torch.cuda.current_stream(model.device))
-            try:
-                with torch.cuda.stream(side):
-                    if group is not None:   # RCCL sets up its communicator at the first collective: outside the capture
-                        _all_reduce_sum(torch.zeros(8, dtype=torch.float64, device=opt_state.x.device), group)
-                    side.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=side):
-                        step()
-                replay = graph.replay
-            except Exception as e:
-                # a failed capture leaves the side stream in an undefined capture state: no silent fallback to call-by-call
-                raise RuntimeError("hipGraph capture of the training step failed" + (" (WF_GRAPH_COLLECTIVE=1: the RCCL all-reduce inside "
-                                   "the graph; unset it to issue the three calls per step instead)" if group is not None else "")) from e
-            torch.cuda.current_stream(model.device).wait_stream(side)
-        fetched = [start_epoch]   # losses of the epochs up to here are on the host
+        st["ws"] = model._workspace(model.train_step_workspace_bytes(per_step), opt_state.x.device)   # allocated here, outside the capture
+        replay = step if not capture else capture_step(model, step, warm_up, "hipGraph capture of the training step failed" + (
+            " (WF_GRAPH_COLLECTIVE=1: the RCCL all-reduce inside the graph; unset it to issue the three calls per step instead)" if group is not None else ""))
 
-        def fetch(upto, keep_last_back=False):
-            torch.cuda.synchronize(model.device)
-            ring = st["ring"].cpu().numpy()
-            new = [float(ring[e % st["ring_len"], 0] / ring[e % st["ring_len"], 2]) for e in range(fetched[0] + 1, upto + 1)]
-            fetched[0] = upto
-            return new
-
-        params = get_params(opt_state)
-        for epoch in range(start_epoch + 1, start_epoch + self.num_epochs + 1):
-            if epoch % self.log_every == 0 or epoch == 1:
-                new = fetch(epoch - 1)
-                loss.extend(new)
-                energies.extend([[v] for v in new])
-                opt_state.version += 1
-                params = get_params(opt_state)
-                ckpt_seed = int(rng.integers(1 << 31))   # (drawn on every rank: the host streams stay aligned)
-                if rank == 0:
-                    helpers.create_checkpoint_wavefunc(ckpt_seed, save_dir, psi, sample, params, epoch, loss, energies, system_dict)
-                    _save_optimizer_state(save_dir, opt_state, epoch)   # (fetch() above synchronised: m, v are those after epoch - 1)
-                model.set_params_device(opt_state.x)
-            replay()
-            if epoch % 100 == 0:
-                new = fetch(epoch)
-                loss.extend(new[:-1])
-                energies.extend([[v] for v in new[:-1]])
-                st["running_average"].fill_(float(np.asarray(loss[-100:]).mean()))   # before this epoch's loss joins (vqmc.py:112-118)
-                loss.append(new[-1])
-                energies.append([new[-1]])
-                if epoch % self.log_every == 0 and verbose:
-                    print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
-        new = fetch(start_epoch + self.num_epochs)
-        loss.extend(new)
-        energies.extend([[v] for v in new])
-        opt_state.version += 1
-        model.set_params_device(opt_state.x)   # every image of the model, evaluation tables included, holds the final parameters
-        return get_params(opt_state), loss, energies
+        def fetched(epoch, new):
+            run.record(new[:-1])
+            st["running_average"].fill_(float(np.asarray(run.loss[-100:]).mean()))   # before this epoch's loss joins (vqmc.py:112-118)
+            run.record(new[-1:])
+            if epoch % self.log_every == 0 and run.verbose:
+                print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
+        return run_device_loop(model, opt_state, run.get_params, replay, loss_ring_reader(model, st, start_epoch + 1), run.record,
+                               start_epoch + 1, start_epoch + self.num_epochs, self.log_every,
+                               lambda epoch, params: run.checkpoint(int(run.rng.integers(1 << 31)), epoch, params, True), 100, fetched)
