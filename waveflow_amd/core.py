@@ -497,6 +497,44 @@ class DeviceModel:
                                             self._stream()), "wf_vqmc_sr_step")
         self._invalidate_host_copy()
 
+    # ---- the SPRING optimiser as a whole step on the device (include/waveflow_sr_spring.h)
+    def make_spring_train_state(self, x, first_step, learning_rate, ring_len=128, defer_eval_tables=False, phi=None):
+        """Device-side state of wf_vqmc_spring_step: that of make_sr_train_state, plus "phi" (the previous direction: float32 cuda [n_params],
+        zeros unless given; updated in place) and "eff_ring" (the step size each step applied after the norm cap; 0 for a skipped step)."""
+        torch = _torch()
+        from . import sr
+        st = self.make_sr_train_state(x, first_step, learning_rate, ring_len=ring_len, defer_eval_tables=defer_eval_tables)
+        if phi is None:
+            phi = torch.zeros(self.n_params, dtype=torch.float32, device=x.device)
+        elif not phi.is_cuda or phi.device != x.device or str(phi.dtype) != "torch.float32" or not phi.is_contiguous() or phi.numel() != self.n_params:
+            raise ValueError(f"phi must be a contiguous float32 cuda vector of {self.n_params} entries on the device of the parameters")
+        st["phi"] = phi
+        st["eff_ring"] = torch.zeros(int(ring_len), dtype=torch.float64, device=x.device)
+        st["c"] = sr.SpringTrainState(x.data_ptr(), st["counter"].data_ptr(), st["step_size"].data_ptr(), st["ring"].data_ptr(),
+                                      st["norm_ring"].data_ptr(), st["status"].data_ptr(), int(ring_len), int(bool(defer_eval_tables)),
+                                      phi.data_ptr(), st["eff_ring"].data_ptr())
+        return st
+
+    def spring_step_workspace_bytes(self, batch):
+        """Workspace of spring_step for `batch` walkers per step; WfError where the library has no such step for this model or batch."""
+        from . import sr
+        return _lib.check(sr.lib().wf_vqmc_spring_step_workspace_bytes(self._h, int(batch)), "wf_vqmc_spring_step_workspace_bytes")
+
+    def spring_step(self, st, seed, batch, protons, damping=0.0, relative_damping=1e-3, momentum=0.0, norm_constraint=0.0, clip=0.0,
+                    exact_sampler=False, walkers=None, out_walkers=None):
+        """One whole SPRING step on the device (wf_vqmc_spring_step): sr_step with momentum (st["phi"]), the step capped at
+        sqrt(norm_constraint) in norm (0: no cap) and local energies clamped `clip` mean absolute deviations around their median (0: not clamped).
+        No host work, no wait, capturable in a hipGraph.  Arguments are checked before anything is launched (ValueError)."""
+        from . import sr
+        damping, relative_damping = sr._check_step(batch, self.D, damping, relative_damping, walkers, out_walkers)
+        momentum, norm_constraint, clip = sr._check_spring(momentum, norm_constraint, clip)
+        ws = self._train_ws(st, self.spring_step_workspace_bytes(batch))
+        x = walkers if walkers is not None else out_walkers
+        _lib.check(sr.lib().wf_vqmc_spring_step(self._h, ctypes.byref(st["c"]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(batch), *self._protons(protons),
+                                                damping, relative_damping, momentum, norm_constraint, clip, int(bool(exact_sampler)), self._p(x),
+                                                int(walkers is None), *ws, self._stream()), "wf_vqmc_spring_step")
+        self._invalidate_host_copy()
+
     def block_sums(self, v):
         """fp64 [sum v, sum v^2, count] on the device (deterministic order)."""
         torch = _torch()

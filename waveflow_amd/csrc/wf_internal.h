@@ -287,6 +287,15 @@ int launch_sr_eloc_rhs(const float* hpsi, const float* psi, int64_t B, float* e_
 int launch_sr_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, int ring_len,
                       const unsigned long long* counter, void* stream);
 int launch_sr_update(float* params, const float* d, int64_t P, const float* step_size, const int32_t* flag, void* stream);
+// the glue of wf_vqmc_spring_step (wf_kernels_sr_spring.hip): inv and e_loc ahead of the rows; the clipped, momentum-corrected and centred right-hand
+// side (B <= 4096; stats[4] = median, mean absolute deviation, the two clamp bounds); the verdict of k_sr_verdict with the capped step size
+// (eff[0], eff_ring: 0 for a skipped step); the guarded update of theta and phi
+int launch_spring_eloc(const float* hpsi, const float* psi, int64_t B, float* e_loc, float* inv, void* stream);
+int launch_spring_rhs(const float* hpsi, const float* psi, int64_t B, const double* q, double mu, double clip, float* e_loc, float* inv, double* rhs,
+                      double* stats, void* stream);
+int launch_spring_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, double* eff_ring, int ring_len,
+                          const unsigned long long* counter, const float* step_size, double cap, float* eff, void* stream);
+int launch_spring_update(float* params, float* phi, const float* d, int64_t P, const float* eff, const int32_t* flag, void* stream);
 
 void set_hip_error(int e);
 

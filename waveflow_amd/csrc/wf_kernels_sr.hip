@@ -17,6 +17,7 @@
 
 #include "../../include/waveflow_sr.h"
 #include "wf_internal.h"
+#include "wf_sr_common.h"
 
 namespace wf {
 
@@ -26,11 +27,7 @@ constexpr int kSrTile = 64;       // rows of O per block tile of the Gram matrix
 constexpr int kSrKs = 32;         // columns of O staged in LDS per step
 constexpr int kSrLds = 36;        // LDS row stride in floats: 16-byte rows, and the 16 rows x 4 columns a wave reads per product hit 64 banks
 constexpr int kSrNb = 32;         // Cholesky panel width
-constexpr int kSrSlab = 32;       // rows per block of the apply pass
 constexpr int64_t kSrMaxSolve = 4096;
-constexpr int64_t kSrMaxRows = 65536;
-
-static int64_t sr_align(int64_t v) { return (v + 255) / 256 * 256; }
 
 // How wf_sr_gram cuts its work for (B, P): block tiles on or below the diagonal, and P chunks (a multiple of the K step) so that about
 // a thousand blocks exist even at B = 128; one chunk where the tiles alone fill the device.
@@ -54,16 +51,6 @@ static int64_t gram_ws_bytes(int64_t B, int64_t P) {
     return (int64_t)g.nsplit * g.ntiles * kSrTile * kSrTile * 8 + sr_align(B * 8) + 256;
 }
 static int64_t solve_ws_bytes(int64_t B) { return sr_align(B * 8); }
-static int64_t apply_ws_bytes(int64_t B, int64_t P) { return sr_align(B * 8) + (B + kSrSlab - 1) / kSrSlab * P * 8; }
-
-static int sr_finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_hip_error((int)e);
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
-}
 
 // tile number t = bi (bi + 1) / 2 + bj  ->  (bi, bj), bi >= bj
 __device__ __forceinline__ void sr_tile_of(int t, int& bi, int& bj) {
@@ -74,39 +61,11 @@ __device__ __forceinline__ void sr_tile_of(int t, int& bi, int& bj) {
     bj = t - i * (i + 1) / 2;
 }
 
-// rows[r][c .. c + 3], of which the entries with r < B and c + i < c_end exist; the others are zeros and nothing of them is read.
-// vec: base and ld allow a 16-byte load at every c that is a multiple of 4.
-__device__ __forceinline__ float4 sr_load4(const float* __restrict__ rows, int64_t ld, int64_t r, int64_t B, int64_t c, int64_t c_end, bool vec) {
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (r >= B || c >= c_end) return v;
-    const float* p = rows + r * ld + c;
-    if (vec && c + 4 <= c_end) return *reinterpret_cast<const float4*>(p);
-    v.x = p[0];
-    if (c + 1 < c_end) v.y = p[1];
-    if (c + 2 < c_end) v.z = p[2];
-    if (c + 3 < c_end) v.w = p[3];
-    return v;
-}
-
 // Nothing of the matrix pipe in flight when the accumulators are read behind a branch (isa_guard's second rule).
 __device__ __forceinline__ void sr_drain_mfma() {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-}
-
-// sum of v over the 256 threads of the block, the same in every thread; one fixed tree
-__device__ __forceinline__ double sr_block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
 }
 
 // ---- Gram matrix
@@ -448,8 +407,6 @@ __global__ __launch_bounds__(256) void k_sr_apply_reduce(const double* __restric
     for (int64_t i = 0; i < nslab; ++i) s += partial[i * P + p];
     out[p] = (float)(scale * s);
 }
-
-static bool sr_vec_ok(const float* rows, int64_t ld) { return ((uintptr_t)rows & 15) == 0 && (ld & 3) == 0; }
 
 }  // namespace wf
 

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "wf_internal.h"
+#include "wf_sr_common.h"
 
 namespace wf {
 
@@ -15,30 +16,6 @@ namespace {
 
 constexpr int kStepBlock = 256;
 constexpr int kNormBlock = 1024;   // |d|^2 over tens of thousands of parameters in one block: the widest one
-
-int finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_hip_error((int)e);
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
-}
-
-// sum of v over the N threads of the block (red[N]), the same in every thread; one fixed tree
-template <int N>
-__device__ __forceinline__ double step_block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = N / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
-}
 
 }  // namespace
 
@@ -54,7 +31,7 @@ __global__ __launch_bounds__(kStepBlock) void k_sr_eloc_rhs(const float* __restr
         e_loc[i] = el;
         s += (double)el;
     }
-    s = step_block_sum<kStepBlock>(s, red);
+    s = sr_block_sum<kStepBlock>(s, red);
     const double mean = s / (double)B;
     for (int64_t i = threadIdx.x; i < B; i += kStepBlock) rhs[i] = (double)e_loc[i] - mean;   // (the thread's own stores)
 }
@@ -69,7 +46,7 @@ __global__ __launch_bounds__(kNormBlock) void k_sr_verdict(const float* __restri
         const double v = (double)d[p];
         s += v * v;
     }
-    s = step_block_sum<kNormBlock>(s, red);
+    s = sr_block_sum<kNormBlock>(s, red);
     if (threadIdx.x != 0) return;
     const int32_t pivot = info[0];
     const bool ok = pivot == 0 && isfinite(s);
@@ -89,19 +66,19 @@ __global__ __launch_bounds__(kStepBlock) void k_sr_update(float* __restrict__ pa
 
 int launch_sr_eloc_rhs(const float* hpsi, const float* psi, int64_t B, float* e_loc, float* inv, double* rhs, void* stream) {
     hipLaunchKernelGGL(k_sr_eloc_rhs, dim3(1), dim3(kStepBlock), 0, (hipStream_t)stream, hpsi, psi, B, e_loc, inv, rhs);
-    return finish();
+    return sr_finish();
 }
 
 int launch_sr_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, int ring_len,
                       const unsigned long long* counter, void* stream) {
     hipLaunchKernelGGL(k_sr_verdict, dim3(1), dim3(kNormBlock), 0, (hipStream_t)stream, d, P, info, status, flag, norm_ring, ring_len, counter);
-    return finish();
+    return sr_finish();
 }
 
 int launch_sr_update(float* params, const float* d, int64_t P, const float* step_size, const int32_t* flag, void* stream) {
     hipLaunchKernelGGL(k_sr_update, dim3((unsigned)((P + kStepBlock - 1) / kStepBlock)), dim3(kStepBlock), 0, (hipStream_t)stream, params, d, P, step_size,
                        flag);
-    return finish();
+    return sr_finish();
 }
 
 }  // namespace wf

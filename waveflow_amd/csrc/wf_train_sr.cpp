@@ -10,25 +10,16 @@
 
 using namespace wf;
 
-namespace {
-
-constexpr int64_t kSrStepMaxBatch = 4096;   // wf_sr_solve
+namespace wf {
 
 // the models the step covers: those of wf_psi_jac (second-order gradients) that wf_hamiltonian_fwd accepts, wave sweeps and sampler with them
-bool model_covered(const wf_model* m) { return grad_supported(m, true) && check_energy_model(m) == WF_OK; }
-
-// What follows the fixed-size vectors in the workspace, in this order: rows, the batch x batch matrix, the workspace of waveflow_sr.h, and one
-// area the sampler (staged form only), the energy sweep and the tape of wf_psi_jac use one after the other.
-struct Layout {
-    int64_t x, hpsi, psi, e_loc, inv, rhs, y, d, scalars, sums_ws, rows, t, sr, tape;   // offsets
-    int64_t sr_bytes, tape_bytes, total;
-};
+bool sr_step_covered(const wf_model* m) { return grad_supported(m, true) && check_energy_model(m) == WF_OK; }
 
 // (capability, not the current state, as wf_vqmc_train_step_workspace_bytes)
-Layout layout_of(const wf_model* m, int64_t batch) {
+SrStepLayout sr_step_layout(const wf_model* m, int64_t batch, bool with_q) {
     const int D = m->desc.n_dim;
     const int64_t P = m->n_params;
-    Layout l{};
+    SrStepLayout l{};
     Bump b;
     l.x = b.take(batch * D * 4);
     l.hpsi = b.take(batch * 4);
@@ -37,8 +28,9 @@ Layout layout_of(const wf_model* m, int64_t batch) {
     l.inv = b.take(batch * 4);
     l.rhs = b.take(batch * 8);
     l.y = b.take(batch * 8);
+    l.q = b.take(with_q ? batch * 8 : 0);
     l.d = b.take(P * 4);
-    l.scalars = b.take(256);   // block sums [3] doubles at 0, the solver's info at 64, the verdict's flag at 68
+    l.scalars = b.take(256);   // the step's own scalars: block sums, the solver's info, the verdict's flag (each step says where)
     l.sums_ws = b.take(block_sums_ws_bytes(batch));
     l.rows = b.take(batch * P * 4);
     l.t = b.take(batch * batch * 8);
@@ -51,14 +43,14 @@ Layout layout_of(const wf_model* m, int64_t batch) {
     return l;
 }
 
-}  // namespace
+}  // namespace wf
 
 extern "C" {
 
 int64_t wf_vqmc_sr_step_workspace_bytes(const wf_model* m, int64_t batch) {
     if (!m || batch < 1) return WF_ERR_INVALID;
-    if (batch > kSrStepMaxBatch || !model_covered(m)) return WF_ERR_UNSUPPORTED;
-    return layout_of(m, batch).total;
+    if (batch > kSrStepMaxBatch || !sr_step_covered(m)) return WF_ERR_UNSUPPORTED;
+    return sr_step_layout(m, batch, false).total;
 }
 
 int wf_vqmc_sr_step(wf_model* m, const wf_sr_train_state* st, uint64_t seed, int64_t batch, const float* protons_host, int32_t n_protons,
@@ -69,9 +61,9 @@ int wf_vqmc_sr_step(wf_model* m, const wf_sr_train_state* st, uint64_t seed, int
     if (!st->params_dev || !st->counter_dev || !st->step_size_dev || !st->loss_ring_dev || !st->status_dev || st->ring_len < 1) return WF_ERR_INVALID;
     if (!(damping_abs >= 0.0) || !(damping_rel >= 0.0) || (damping_abs == 0.0 && damping_rel == 0.0)) return WF_ERR_INVALID;
     if (!draw && !x_dev) return WF_ERR_INVALID;
-    if (batch > kSrStepMaxBatch || !model_covered(m)) return WF_ERR_UNSUPPORTED;
+    if (batch > kSrStepMaxBatch || !sr_step_covered(m)) return WF_ERR_UNSUPPORTED;
     if (!m->params_set || !workspace_dev) return WF_ERR_INVALID;
-    const Layout l = layout_of(m, batch);
+    const SrStepLayout l = sr_step_layout(m, batch, false);
     if (workspace_bytes < l.total) return WF_ERR_INVALID;
     DeviceGuard g(m->device);
     const int D = m->desc.n_dim;
@@ -81,7 +73,7 @@ int wf_vqmc_sr_step(wf_model* m, const wf_sr_train_state* st, uint64_t seed, int
     float *hpsi = (float*)(w + l.hpsi), *psi = (float*)(w + l.psi), *e_loc = (float*)(w + l.e_loc), *inv = (float*)(w + l.inv);
     double *rhs = (double*)(w + l.rhs), *y = (double*)(w + l.y), *sums = (double*)(w + l.scalars), *t = (double*)(w + l.t);
     float *d = (float*)(w + l.d), *rows = (float*)(w + l.rows);
-    int32_t *info = (int32_t*)(w + l.scalars + 64), *flag = info + 1;
+    int32_t *info = (int32_t*)(w + l.scalars + 64), *flag = info + 1;   // scalars: block sums [3] doubles at 0, info at 64, flag at 68
     void *sums_ws = w + l.sums_ws, *sr_ws = w + l.sr, *tape = w + l.tape;
     unsigned long long* counter = (unsigned long long*)st->counter_dev;
     int rc = WF_OK;

@@ -1,6 +1,7 @@
 """Stochastic reconfiguration (the natural gradient of variational Monte Carlo) from per-walker Jacobian rows, in its B x B ("minSR") form:
 the ctypes surface of include/waveflow_sr.h, and of include/waveflow_sr_step.h (the whole training step on the device: STEP_PROTOTYPES,
-SrTrainState; core.DeviceModel.sr_step drives it).
+SrTrainState; core.DeviceModel.sr_step drives it), and of include/waveflow_sr_spring.h (the SPRING optimiser: SPRING_PROTOTYPES, SpringTrainState,
+`matvec`, `apply_add`, `spring_rhs`, `clip_local_energies`, `spring_direction`; core.DeviceModel.spring_step drives the whole step).
 
 With O[b][k] = d ln psi_b / d theta_k, local energies e, H = I - 1 1^T / B and lambda > 0,
     d = (O^T H O / B + lambda I)^-1 (2 / B) O^T H e  =  (2 / B) O^T H y,    (H O O^T H / B + lambda I) y = H e
@@ -37,6 +38,22 @@ STEP_PROTOTYPES = {
     "wf_vqmc_sr_step": (_i32, [_vp, ctypes.POINTER(SrTrainState), ctypes.c_uint64, _i64, _vp, _i32, _f64, _f64, _i32, _vp, _i32] + _ws + [_vp]),
 }
 
+
+class SpringTrainState(ctypes.Structure):
+    """wf_spring_train_state (include/waveflow_sr_spring.h): the fields of SrTrainState, then the previous direction and the ring of step sizes"""
+    _fields_ = SrTrainState._fields_ + [("phi_dev", _vp), ("eff_ring_dev", _vp)]
+
+
+# name -> (restype, argtypes): every function of include/waveflow_sr_spring.h, in its order (tests/test_sr_spring_host.py)
+SPRING_PROTOTYPES = {
+    "wf_sr_matvec": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "wf_sr_apply_add": (_i32, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _f64, _vp] + _ws + [_vp]),
+    "wf_spring_rhs": (_i32, [_vp, _vp, _i64, _vp, _f64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "wf_vqmc_spring_step_workspace_bytes": (_i64, [_vp, _i64]),
+    "wf_vqmc_spring_step": (_i32, [_vp, ctypes.POINTER(SpringTrainState), ctypes.c_uint64, _i64, _vp, _i32, _f64, _f64, _f64, _f64, _f64, _i32, _vp, _i32]
+                            + _ws + [_vp]),
+}
+
 _bound = None
 
 
@@ -49,11 +66,11 @@ class NotPositiveDefinite(ArithmeticError):
 
 
 def lib():
-    """The handle of _lib.lib() with PROTOTYPES and STEP_PROTOTYPES applied to it."""
+    """The handle of _lib.lib() with PROTOTYPES, STEP_PROTOTYPES and SPRING_PROTOTYPES applied to it."""
     global _bound
     L = _lib.lib()
     if _bound is not L:
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(STEP_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(STEP_PROTOTYPES.items()) + list(SPRING_PROTOTYPES.items()):
             f = getattr(L, name)
             f.restype = restype
             f.argtypes = argtypes
@@ -92,6 +109,18 @@ def _check_step(batch, n_dim, damping, relative_damping, walkers, out_walkers):
         if not t.is_cuda:
             raise ValueError(f"{what} must be a cuda tensor: stochastic reconfiguration has no CPU fallback")
     return damping, relative_damping
+
+
+def _check_spring(momentum, norm_constraint, clip):
+    """-> (momentum in [0, 1), norm cap >= 0, clip factor >= 0) as floats"""
+    momentum, norm_constraint, clip = float(momentum), float(norm_constraint), float(clip)
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError(f"momentum must lie in [0, 1), got {momentum}")
+    if not norm_constraint >= 0.0:
+        raise ValueError(f"the norm constraint must be >= 0 (0: none), got {norm_constraint}")
+    if not clip >= 0.0:
+        raise ValueError(f"the clip factor must be >= 0 (0: no clipping), got {clip}")
+    return momentum, norm_constraint, clip
 
 
 def _check_rows(rows, limit=None):
@@ -212,6 +241,122 @@ def natural_gradient(rows, e_loc, damping=0.0, relative_damping=1e-3):
     e = e_loc.double()
     y, info = _solve(T, B, e - e.mean(), damping, relative_damping, ws)
     d = _apply(rows, B, P, ld, y, 2.0 / B, ws)
+    pivot = int(info.item())
+    if pivot != 0:
+        raise NotPositiveDefinite(pivot)
+    return d
+
+
+# ---- SPRING (include/waveflow_sr_spring.h)
+
+def _matvec(rows, B, P, ld, v):
+    import torch
+    q = torch.empty(B, dtype=torch.float64, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(lib().wf_sr_matvec(rows.data_ptr(), B, P, ld, v.data_ptr(), q.data_ptr(), _lib.stream_ptr(rows.device)), "wf_sr_matvec")
+    return q
+
+
+def _apply_add(rows, B, P, ld, y, scale, prev, mu, out, ws):
+    import torch
+    with torch.cuda.device(rows.device):
+        _lib.check(lib().wf_sr_apply_add(rows.data_ptr(), B, P, ld, y.data_ptr(), float(scale), None if prev is None else prev.data_ptr(), float(mu),
+                                         out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(rows.device)), "wf_sr_apply_add")
+    return out
+
+
+def matvec(rows, v):
+    """q[b] = sum_p rows[b][p] v[p] -> float64 cuda [B]: fp32 operands, exact products, fp64 sums in a fixed order (wf_sr_matvec)."""
+    import torch
+    B, P, ld = _check_rows(rows)
+    _check_vector(v, P, torch.float32, "v", rows.device)
+    return _matvec(rows, B, P, ld, v.contiguous())
+
+
+def apply_add(rows, y, scale, prev=None, mu=0.0, out=None, workspace=None):
+    """out[p] = fl32(mu * prev[p] + scale * sum_b (y_b - mean y) rows[b][p]) -> float32 cuda [P]; prev None or mu 0: the bits of `apply`.
+    `out` (float32 cuda [P], contiguous) may be `prev` itself (wf_sr_apply_add)."""
+    import torch
+    B, P, ld = _check_rows(rows)
+    _check_vector(y, B, torch.float64, "y", rows.device)
+    mu = _check_spring(mu, 0.0, 0.0)[0]
+    for what, t in (("prev", prev), ("out", out)):
+        if t is not None:
+            _check_vector(t, P, torch.float32, what, rows.device)
+            if not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=rows.device)
+    return _apply_add(rows, B, P, ld, y.contiguous(), scale, prev, mu, out, workspace if workspace is not None else _workspace(B, P, rows.device))
+
+
+def spring_rhs(hpsi, psi, q=None, momentum=0.0, clip=0.0):
+    """The right-hand side of the SPRING solve as the device step computes it (wf_spring_rhs): hpsi, psi float32 cuda [B], q float64 cuda [B]
+    (needed when momentum > 0) -> (e_loc, inv float32 [B], rhs float64 [B], stats float64 [4] = median, mean absolute deviation, clamp bounds)."""
+    import torch
+    momentum, _, clip = _check_spring(momentum, 0.0, clip)
+    if not hasattr(hpsi, "is_cuda") or hpsi.dim() != 1 or hpsi.numel() < 1 or hpsi.numel() > MAX_WALKERS:
+        raise ValueError(f"hpsi must be a vector of 1 .. {MAX_WALKERS} entries")
+    if not hpsi.is_cuda:
+        raise ValueError("hpsi must be a cuda tensor: stochastic reconfiguration has no CPU fallback")
+    B, dev = hpsi.numel(), hpsi.device
+    _check_vector(hpsi, B, torch.float32, "hpsi", dev)
+    _check_vector(psi, B, torch.float32, "psi", dev)
+    if momentum != 0.0 and q is None:
+        raise ValueError("momentum > 0 needs q = rows @ prev (matvec)")
+    if q is not None:
+        _check_vector(q, B, torch.float64, "q", dev)
+        q = q.contiguous()
+    hpsi, psi = hpsi.contiguous(), psi.contiguous()
+    e_loc, inv = torch.empty_like(hpsi), torch.empty_like(hpsi)
+    rhs, stats = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib().wf_spring_rhs(hpsi.data_ptr(), psi.data_ptr(), B, None if q is None else q.data_ptr(), momentum, clip, e_loc.data_ptr(),
+                                       inv.data_ptr(), rhs.data_ptr(), stats.data_ptr(), _lib.stream_ptr(dev)), "wf_spring_rhs")
+    return e_loc, inv, rhs, stats
+
+
+def _median_and_deviation(e32):
+    """(c, w) of float32 e_b as float64 scalars: c the median (even B: the mean of the two middle values; values that are not finite count as
+    +inf and so sort last), w = mean |e_b - c|."""
+    import torch
+    B = e32.numel()
+    key = torch.where(torch.isfinite(e32), e32, torch.full_like(e32, float("inf"))).sort().values.double()
+    c = key[B // 2] if B % 2 else 0.5 * (key[B // 2 - 1] + key[B // 2])
+    return c, (e32.double() - c).abs().mean()
+
+
+def clip_local_energies(e_loc, clip):
+    """clamp(e_b, c - k w, c + k w) in float64, c the median of the float32 e_b (even B: the mean of the two middle values; values that are not
+    finite sort last), w = mean |e_b - c|; clip == 0: e_loc as float64, unchanged.  The eager counterpart of the device step's clamp."""
+    import torch
+    e32 = e_loc.float()
+    e = e32.double()
+    if float(clip) == 0.0:
+        return e
+    c, w = _median_and_deviation(e32)
+    return torch.minimum(torch.maximum(e, c - float(clip) * w), c + float(clip) * w)
+
+
+def spring_direction(rows, e_loc, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0):
+    """The SPRING direction d = mu prev + (2 / B) O^T H y with (Tbar + lambda I) y = H (e~ - (mu / 2) O prev), the minimiser of
+    (1 / B) |H O d - 2 H e~|^2 + lambda |d - mu prev|^2; e~ = clip_local_energies(e_loc, clip); momentum 0 gives natural_gradient.
+    rows [B, P] float32 cuda, e_loc [B], prev float32 cuda [P] (the previous d; zeros at the start) -> float32 cuda [P].  Library calls on the
+    current stream, then one read of the solver's status: NotPositiveDefinite if a pivot was not positive."""
+    import torch
+    damping, relative_damping = _check_damping(damping, relative_damping)
+    momentum, _, clip = _check_spring(momentum, 0.0, clip)
+    B, P, ld = _check_rows(rows, limit=MAX_WALKERS)
+    _check_vector(e_loc, B, None, "e_loc", rows.device)
+    _check_vector(prev, P, torch.float32, "prev", rows.device)
+    prev = prev.contiguous()
+    ws = _workspace(B, P, rows.device)
+    r = clip_local_energies(e_loc, clip)
+    if momentum != 0.0:
+        r = r - (0.5 * momentum) * _matvec(rows, B, P, ld, prev)
+    T = _gram(rows, B, P, ld, ws)
+    y, info = _solve(T, B, r - r.mean(), damping, relative_damping, ws)
+    d = _apply_add(rows, B, P, ld, y, 2.0 / B, prev, momentum, torch.empty(P, dtype=torch.float32, device=rows.device), ws)
     pivot = int(info.item())
     if pivot != 0:
         raise NotPositiveDefinite(pivot)

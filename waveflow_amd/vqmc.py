@@ -283,6 +283,66 @@ def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **
     return checkpoint.unflatten_like(params, flat - np.float32(lr) * d.cpu().numpy()), loss_val
 
 
+def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0, group=None):
+    """The SPRING direction on the walkers of `batch` (sr.spring_direction on the rows and local energies of sr_natural_gradient): stochastic
+    reconfiguration pulled towards momentum * prev, local energies clamped `clip` mean absolute deviations around their median (0: not clamped).
+    prev: the previous direction, float32 cuda [n_params] (zeros at the start).  -> (d float32 cuda [n_params], loss = mean of the unclipped e_loc).
+    Sharded walkers (`group`) are not supported."""
+    from . import sr
+    if group is not None:
+        raise NotImplementedError("SPRING over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
+    sr._check_damping(damping, relative_damping)
+    sr._check_spring(momentum, 0.0, clip)
+    model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
+    inv = 1.0 / (ps + 1e-8)
+    e_loc = hpsi * inv
+    rows = model.psi_jacobian(x, w_psi=inv)
+    d = sr.spring_direction(rows, e_loc, prev.to(rows.device), momentum, damping=damping, relative_damping=relative_damping, clip=clip)
+    return d, float(e_loc.double().mean())
+
+
+def spring_step_size(learning_rate, d, norm_constraint):
+    """float32 min(lr, sqrt(C / |d|^2)) with |d|^2 in float64; lr itself when C == 0 or d == 0 (the device step's rule)."""
+    norm2 = float((d.double() ** 2).sum())
+    eff = float(learning_rate)
+    if float(norm_constraint) != 0.0 and norm2 != 0.0:
+        eff = min(eff, float(np.sqrt(float(norm_constraint) / norm2)))
+    return float(np.float32(eff))
+
+
+def train_step_spring(epoch, psi, h_fn, params, batch, learning_rate, prev, momentum, norm_constraint, clip, group=None, **damping):
+    """One SPRING step theta <- theta - eff d with d = spring_direction(...) and eff = spring_step_size(lr, d, norm_constraint)
+    -> (new params, d, loss); the caller passes d as `prev` of the next step.  `params` is left as it is, as in train_step_sr."""
+    from . import sr
+    sr._check_spring(momentum, norm_constraint, clip)
+    d, loss_val = spring_direction(params, psi, h_fn, batch, prev, momentum, clip=clip, group=group, **damping)
+    eff = spring_step_size(_lr_at(learning_rate, epoch), d, norm_constraint)
+    if isinstance(params, DeviceParams):
+        return DeviceParams(params.template, params.flat - eff * d.to(params.flat.device), params.version + 1), d, loss_val
+    flat = flatten_params(params).astype(np.float32)
+    return checkpoint.unflatten_like(params, flat - np.float32(eff) * d.cpu().numpy()), d, loss_val
+
+
+def _save_spring_state(save_dir, phi, epoch):
+    """SPRING's previous direction next to the checkpoints, as Adam's moments are: `spring_state.npz` {phi, epoch}."""
+    tmp = f"{save_dir}/spring_state.tmp.npz"
+    np.savez(tmp, phi=phi.detach().cpu().numpy(), epoch=np.int64(epoch))
+    os.replace(tmp, f"{save_dir}/spring_state.npz")
+
+
+def _load_spring_state(save_dir, phi, epoch):
+    """-> True when the direction of exactly this checkpoint epoch was restored into phi."""
+    path = f"{save_dir}/spring_state.npz"
+    if not os.path.isfile(path):
+        return False
+    with np.load(path) as z:
+        if int(z["epoch"]) != int(epoch) or z["phi"].shape != tuple(phi.shape):
+            return False
+        import torch
+        phi.copy_(torch.as_tensor(z["phi"].astype(np.float32)))
+    return True
+
+
 def _save_optimizer_state(save_dir, opt_state, epoch):
     """Adam's moments next to the reference's artefacts (the reference checkpoints parameters only, vqmc.py:96-100, and a restart
     there begins with a fresh optimiser): `optimizer_state.npz` {m, v, epoch}, rewritten at every checkpoint."""
@@ -390,6 +450,13 @@ class _Run(SimpleNamespace):
             helpers.create_checkpoint_wavefunc(seed, self.save_dir, self.psi, self.sample, params, epoch, self.loss, self.energies, self.system_dict)
             if save_optimizer:
                 _save_optimizer_state(self.save_dir, self.opt_state, epoch)
+            if getattr(self, "save_extra", None) is not None:
+                self.save_extra(epoch)
+
+
+# optimizer='spring': the settings tests/test_gpu_sr_spring.py trains He with (learning rate 0.1 there), measured on the MI355X -- DESIGN 4.21.
+# relative_damping is what an empty sr_damping means under 'spring' (under 'sr' it stays train_step_sr's 1e-3).
+SPRING_DEFAULTS = {"momentum": 0.9, "norm_constraint": 0.1, "clip": 5.0, "relative_damping": 1e-2}
 
 
 class ModelTrainer:
@@ -417,7 +484,11 @@ class ModelTrainer:
         self.exact_sampler = False   # False: the reference's sampler (made.py:88 quirk); True: draws from |psi|^2
         self.optimizer = 'adam'      # 'sr': stochastic reconfiguration steps (train_step_sr; eager unless sr_on_device), one process
         self.sr_damping = {}         # damping / relative_damping of train_step_sr (its defaults when empty)
-        self.sr_on_device = False    # optimizer='sr' only: True runs the whole step on the device (wf_vqmc_sr_step), captured once when use_graph
+        self.sr_on_device = False    # optimizer='sr' / 'spring': True runs the whole step on the device (wf_vqmc_sr_step / wf_vqmc_spring_step), captured once when use_graph
+        # optimizer='spring': train_step_spring (sr_on_device as for 'sr'; an empty sr_damping means SPRING_DEFAULTS['relative_damping']); DESIGN 4.21
+        self.spring_momentum = SPRING_DEFAULTS["momentum"]
+        self.spring_norm_constraint = SPRING_DEFAULTS["norm_constraint"]   # the step is capped at sqrt(this) in norm; 0: no cap
+        self.spring_clip = SPRING_DEFAULTS["clip"]                         # local energies clamped this many mean absolute deviations around the median; 0: off
 
     def start_training(self, restart=False, verbose=True, group=None):
         """Under torch.distributed (one process per GPU, `torchrun examples/run_vqmc.py`) the walkers of a step are split over
@@ -425,11 +496,11 @@ class ModelTrainer:
         stream, and the step's single all-reduce (gradient + energy moments) keeps the replicas identical; rank 0 writes."""
         import torch.distributed as dist
         optimizer = getattr(self, "optimizer", "adam")
-        if optimizer not in ('adam', 'sr'):
-            raise ValueError(f"optimizer must be 'adam' or 'sr', got {optimizer!r}")
+        if optimizer not in ('adam', 'sr', 'spring'):
+            raise ValueError(f"optimizer must be 'adam', 'sr' or 'spring', got {optimizer!r}")
         distributed = dist.is_available() and dist.is_initialized()
-        if optimizer == 'sr' and (distributed or group is not None):
-            raise NotImplementedError("optimizer='sr' runs in one process: stochastic reconfiguration over sharded walkers is not implemented")
+        if optimizer in ('sr', 'spring') and (distributed or group is not None):
+            raise NotImplementedError(f"optimizer={optimizer!r} runs in one process: stochastic reconfiguration over sharded walkers is not implemented")
         if distributed and group is None:
             group = dist.group.WORLD   # (None would read as "not distributed" further down: the default group, explicitly)
         rank = dist.get_rank(group) if distributed else 0
@@ -451,7 +522,7 @@ class ModelTrainer:
             import torch
             opt_state.x.copy_(torch.as_tensor(flatten_params(params).astype(np.float32)))
             opt_state.version += 1
-            if not _load_optimizer_state(save_dir, opt_state, start_epoch):
+            if optimizer != 'spring' and not _load_optimizer_state(save_dir, opt_state, start_epoch):
                 # (a directory written by the reference, or by an older run): the moments restart from zero while the step index
                 # -- and with it Adam's bias correction -- continues, so the first ~10 steps are up to 3x the nominal size
                 import warnings
@@ -481,6 +552,8 @@ class ModelTrainer:
                 fused = False
         if optimizer == 'sr':
             params = (self._train_sr_device if getattr(self, "sr_on_device", False) else self._train_sr)(run)
+        elif optimizer == 'spring':
+            params = (self._train_spring_device if getattr(self, "sr_on_device", False) else self._train_spring)(run)
         elif fused:
             params = self._train_graphed(run)
         else:
@@ -578,6 +651,108 @@ class ModelTrainer:
         return run_device_loop(model, opt_state, run.get_params, replay, loss_ring_reader(model, st, start_epoch + 1, after=status), run.record,
                                start_epoch + 1, start_epoch + self.num_epochs, self.log_every,
                                lambda epoch, params: run.checkpoint(int(run.rng.integers(1 << 31)), epoch, params, False), 100, fetched)
+
+    def _spring_damping(self):
+        return getattr(self, "sr_damping", None) or {"relative_damping": SPRING_DEFAULTS["relative_damping"]}
+
+    def _spring_settings(self):
+        return (float(getattr(self, "spring_momentum", SPRING_DEFAULTS["momentum"])),
+                float(getattr(self, "spring_norm_constraint", SPRING_DEFAULTS["norm_constraint"])),
+                float(getattr(self, "spring_clip", SPRING_DEFAULTS["clip"])))
+
+    def _spring_phi(self, run):
+        """The previous direction on the device of the parameters: zeros, or on a restart what the checkpoint's epoch saved."""
+        import torch
+        import warnings
+        phi = torch.zeros_like(run.opt_state.x)
+        if run.start_epoch > 0 and not _load_spring_state(run.save_dir, phi, run.start_epoch):
+            warnings.warn(f"{run.save_dir}/spring_state.npz does not match checkpoint epoch {run.start_epoch}: SPRING's momentum restarts from zero")
+        run.save_extra = lambda epoch: _save_spring_state(run.save_dir, phi, epoch)
+        return phi
+
+    def _train_spring(self, run):
+        """The host-stepped loop with train_step_spring: eager, parameters in opt_state.x, the previous direction carried from step to step and saved
+        with every checkpoint.  At the end the number of steps the norm cap bound is reported (self.spring_capped_steps)."""
+        momentum, cap, clip = self._spring_settings()
+        phi = self._spring_phi(run)
+        capped = [0]
+
+        def step(epoch, params, batch):
+            new_params, d, new_loss = train_step_spring(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, phi, momentum, cap, clip,
+                                                        **self._spring_damping())
+            capped[0] += int(spring_step_size(_lr_at(self.learning_rate, epoch), d, cap) < float(np.float32(_lr_at(self.learning_rate, epoch))))
+            phi.copy_(d)
+            run.opt_state.x.copy_(new_params.flat)
+            run.opt_state.version += 1
+            return new_loss
+        params = self._train_host(run, step, save_optimizer=False)
+        self.spring_capped_steps, self.spring_skipped_steps = capped[0], 0
+        if run.verbose:
+            print(f"SPRING: the norm constraint bound {capped[0]} of {self.num_epochs} steps")
+        return params
+
+    def _train_spring_device(self, run):
+        """optimizer='spring' with sr_on_device: run_device_loop around wf_vqmc_spring_step, exactly as _train_sr_device around wf_vqmc_sr_step.  With
+        the loss ring the host reads the step's status and the ring of applied step sizes: skipped steps are reported once, with their count; the
+        steps the norm cap bound are counted (self.spring_capped_steps) and reported at the end with the skipped ones."""
+        import warnings
+        model, opt_state, start_epoch = run.psi.model, run.opt_state, run.start_epoch
+        lr = self.learning_rate
+        damping = self._spring_damping()
+        momentum, cap, clip = self._spring_settings()
+        batch = int(self.batch_size)
+        phi = self._spring_phi(run)
+        st = model.make_spring_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True, phi=phi)
+        model.set_params_device(opt_state.x)
+        seed = int(run.rng.integers(1 << 62))
+
+        def step():
+            model.spring_step(st, seed, batch, run.h_fn.protons, exact_sampler=self.exact_sampler, momentum=momentum, norm_constraint=cap, clip=clip, **damping)
+        st["ws"] = model._workspace(model.spring_step_workspace_bytes(batch), opt_state.x.device)   # allocated here, outside the capture
+        phi0 = phi.clone()
+
+        def warm_up():
+            # one step outside the capture at learning rate 0: the parameters come out bitwise as they went in; the direction it left in phi,
+            # the counter, the rings and the status are put back
+            step()
+            phi.copy_(phi0)
+            st["counter"].fill_(start_epoch + 1)
+            for name in ("ring", "norm_ring", "eff_ring", "status"):
+                st[name].zero_()
+        launch = capture_step(model, step, warm_up, "hipGraph capture of the SPRING step failed") if self.use_graph else step
+        if callable(lr):   # a schedule: the rate of its epoch in front of every step
+            epochs = iter(range(start_epoch + 1, start_epoch + self.num_epochs + 1))
+
+            def replay():
+                st["step_size"].fill_(_lr_at(lr, next(epochs)))
+                launch()
+        else:
+            st["step_size"].fill_(float(lr))
+            replay = launch
+        warned, seen, capped = [False], [start_epoch], [0]
+
+        def status(upto):
+            info, skipped = (int(v) for v in st["status"].cpu().tolist())
+            eff = st["eff_ring"].cpu().numpy()
+            for e in range(seen[0] + 1, upto + 1):
+                capped[0] += int(0.0 < eff[e % st["ring_len"]] < float(np.float32(_lr_at(lr, e))))
+            seen[0] = max(seen[0], upto)
+            self.spring_capped_steps, self.spring_skipped_steps = capped[0], skipped
+            if skipped and not warned[0]:
+                warned[0] = True
+                warnings.warn(f"SPRING: {skipped} of the first {upto - start_epoch} steps were skipped (status of the last step: {info}; > 0: that pivot of "
+                              f"the shifted B x B matrix is not positive, -1: the step is not finite) -- more damping")
+
+        def fetched(epoch, new):
+            run.record(new)
+            if epoch % self.log_every == 0 and run.verbose:
+                print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
+        params = run_device_loop(model, opt_state, run.get_params, replay, loss_ring_reader(model, st, start_epoch + 1, after=status), run.record,
+                                 start_epoch + 1, start_epoch + self.num_epochs, self.log_every,
+                                 lambda epoch, params: run.checkpoint(int(run.rng.integers(1 << 31)), epoch, params, False), 100, fetched)
+        if run.verbose:
+            print(f"SPRING: the norm constraint bound {capped[0]} and the solver skipped {self.spring_skipped_steps} of {self.num_epochs} steps")
+        return params
 
     def _train_graphed(self, run):
         """The training loop with the step captured once in a hipGraph (run_device_loop): per epoch one graph launch; the host looks at the
