@@ -535,6 +535,34 @@ class DeviceModel:
                                                 int(walkers is None), *ws, self._stream()), "wf_vqmc_spring_step")
         self._invalidate_host_copy()
 
+    # ---- one measurement step on the device (include/waveflow_observe.h; observables.measure drives it)
+    def observe_step_workspace_bytes(self, batch):
+        """Workspace of observe_step for `batch` walkers per step; WfError where the library has no such step for this model or batch."""
+        from . import observables
+        return _lib.check(observables.lib().wf_vqmc_observe_step_workspace_bytes(self._h, int(batch)), "wf_vqmc_observe_step_workspace_bytes")
+
+    def observe_step(self, acc, counter, seed, batch, protons, exact_sampler=False, walkers=None, out_walkers=None, values=None):
+        """One measurement step on the device (wf_vqmc_observe_step): no host work, no wait, capturable in a hipGraph after one call outside the
+        capture.  The step draws its walkers (stream `seed` advanced by `counter`, one int64 on the device, + 1 at the end; out_walkers [batch, D],
+        if given, receives them) or reads them from `walkers` [batch, D]; it adds them to `acc` (an observables.Accumulator; None with `values`)
+        and writes the per-walker values to `values` [batch, 5] if given.  Nothing of the model changes.  Arguments are checked before anything
+        is launched (ValueError)."""
+        from . import observables
+        batch = observables._check_step(batch, self.D, walkers, out_walkers, values)
+        if acc is None and values is None:
+            raise ValueError("nothing to do: neither an accumulator nor values")
+        if acc is not None and acc.D != self.D:
+            raise ValueError(f"the accumulator holds {acc.D} columns, the model has {self.D}")
+        if not hasattr(counter, "is_cuda") or counter.numel() != 1 or str(counter.dtype) != "torch.int64" or not counter.is_cuda:
+            raise ValueError("counter must be one int64 on the device (no CPU fallback)")
+        st = acc.st if acc is not None else {"x": counter, "ws": None}
+        ws = self._train_ws(st, self.observe_step_workspace_bytes(batch))
+        x = walkers if walkers is not None else out_walkers
+        _lib.check(observables.lib().wf_vqmc_observe_step(self._h, ctypes.byref(acc.c) if acc is not None else None, self._p(counter),
+                                                          int(seed) & 0xFFFFFFFFFFFFFFFF, batch, *self._protons(protons), int(bool(exact_sampler)),
+                                                          self._p(x), int(walkers is None), self._p(values), *ws, self._stream()),
+                   "wf_vqmc_observe_step")
+
     def block_sums(self, v):
         """fp64 [sum v, sum v^2, count] on the device (deterministic order)."""
         torch = _torch()
