@@ -563,6 +563,42 @@ class DeviceModel:
                                                           self._p(x), int(walkers is None), self._p(values), *ws, self._stream()),
                    "wf_vqmc_observe_step")
 
+    # ---- fixed-node diffusion Monte Carlo on the device (include/waveflow_dmc.h; dmc.run drives it)
+    def dmc_workspace_bytes(self, n_walkers):
+        """Workspace of dmc_init and dmc_step for a population of n_walkers; WfError where the library has no such step for this model or size."""
+        from . import dmc
+        return _lib.check(dmc.lib().wf_vqmc_dmc_workspace_bytes(self._h, int(n_walkers)), "wf_vqmc_dmc_workspace_bytes")
+
+    def make_dmc_state(self, n_walkers, ring_len=1024):
+        """-> dmc.State: the device tensors of a population of n_walkers on this model's device (filled by dmc_init)."""
+        from . import dmc
+        return dmc.State(n_walkers, self.D, ring_len, f"cuda:{self.device}")
+
+    def dmc_init(self, state, seed, protons, exact_sampler=True, walkers=None):
+        """Fills `state` (wf_vqmc_dmc_init): its walkers from |psi|^2 (stream `seed`) or copied from `walkers` [n, D] (contiguous float32 cuda),
+        psi, grad and e_loc on them, E_T their mean local energy, one comb that replaces walkers that are not finite, counter 0."""
+        from . import dmc
+        if walkers is not None:
+            dmc._float_tensor(walkers, (state.n, self.D), "walkers", state.device)
+        if state.D != self.D:
+            raise ValueError(f"the state holds {state.D} columns, the model has {self.D}")
+        ws = self._train_ws(state.st, self.dmc_workspace_bytes(state.n))
+        _lib.check(dmc.lib().wf_vqmc_dmc_init(self._h, ctypes.byref(state.c), int(seed) & 0xFFFFFFFFFFFFFFFF, state.n, *self._protons(protons),
+                                              int(bool(exact_sampler)), self._p(walkers), int(walkers is None), *ws, self._stream()),
+                   "wf_vqmc_dmc_init")
+
+    def dmc_step(self, state, seed, protons, tau, limit_drift=False, e_cut=0.0):
+        """One DMC generation on the device (wf_vqmc_dmc_step): propose, wf_psi_coord_derivs at the proposals, accept, the comb, the ring record,
+        E_T, counter + 1.  No host work, no wait, capturable in a hipGraph after one call outside the capture.  Nothing of the model changes.
+        Arguments are checked before anything is launched (ValueError)."""
+        from . import dmc
+        tau, e_cut = dmc._check_tau(tau, e_cut)
+        if state.D != self.D:
+            raise ValueError(f"the state holds {state.D} columns, the model has {self.D}")
+        ws = self._train_ws(state.st, self.dmc_workspace_bytes(state.n))
+        _lib.check(dmc.lib().wf_vqmc_dmc_step(self._h, ctypes.byref(state.c), int(seed) & 0xFFFFFFFFFFFFFFFF, state.n, *self._protons(protons), tau,
+                                              int(bool(limit_drift)), e_cut, *ws, self._stream()), "wf_vqmc_dmc_step")
+
     def block_sums(self, v):
         """fp64 [sum v, sum v^2, count] on the device (deterministic order)."""
         torch = _torch()

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "wf_eloc.h"
 #include "wf_observe.h"
 
 namespace wf {
@@ -64,38 +65,15 @@ __global__ __launch_bounds__(kObsBlock) void k_observe(const float* __restrict__
         }
         const float ps = psi[b];
         fin = fin && isfinite(ps);
-        const float inv = __fdiv_rn(1.0f, __fadd_rn(ps, 1e-8f));
-        float lap = 0.0f, tg = 0.0f;
+        float gr[D], hd[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const float gd = grad[b * D + d], hd = hdiag[b * D + d];
-            fin = fin && isfinite(gd) && isfinite(hd);
-            lap = d == 0 ? hd : __fadd_rn(lap, hd);
-            const float t = __fmul_rn(gd, inv);
-            tg = __fadd_rn(tg, __fmul_rn(t, t));
+            gr[d] = grad[b * D + d];
+            hd[d] = hdiag[b * D + d];
+            fin = fin && isfinite(gr[d]) && isfinite(hd[d]);
         }
-        // the potential: the two loops of k_vqmc_seeds (wf_kernels_grad.hip), kept as two numbers
-        float v_en = 0.0f, v_ee = 0.0f;
-        for (int p = 0; p < pr.n; ++p)
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                const float r = pr.pos[p] - x[d];
-                v_en -= 1.0f / sqrtf(1.0f + r * r);
-            }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < i; ++j) {
-                const float r = x[i] - x[j];
-                v_ee += 1.0f / sqrtf(1.0f + r * r);
-            }
-        const float half_lap = __fmul_rn(-0.5f, lap);
         float v[WF_OBSERVE_SCALARS];
-        v[0] = __fmul_rn(__fadd_rn(half_lap, __fmul_rn(__fadd_rn(v_en, v_ee), ps)), inv);
-        v[1] = __fmul_rn(half_lap, inv);
-        v[2] = __fmul_rn(0.5f, tg);
-        v[3] = v_en;
-        v[4] = v_ee;
+        local_values<D>(x, ps, gr, hd, pr, v);   // the rule of the header (wf_eloc.h)
 #pragma unroll
         for (int k = 0; k < WF_OBSERVE_SCALARS; ++k) {
             fin = fin && isfinite(v[k]);
