@@ -49,6 +49,7 @@ extern "C" {
 #define WF_ABI_VERSION 2
 #define WF_MAX_DIM 16
 #define WF_MAX_BC 4
+#define WF_RQS_MAX_BINS 159   /* wf_rqs_fwd: 256 rows of K + 1 floats staged in LDS, (K + 1) KiB <= the 160 KiB of a CU */
 
 typedef enum {
     WF_OK = 0,
@@ -368,7 +369,11 @@ int wf_vqmc_seeds(const float* x_dev, int64_t B, int32_t n_dim, const float* pro
  * parity unpinned).  x[N]; uw, uh [N][K] unnormalised widths / heights; ud [N][n_deriv] unnormalised derivatives with
  * n_deriv == K-1 (unconstrained_RQS: identity outside [left, right], boundary derivatives 1) or K+1 (RQS: explicit).
  * inverse != 0 applies the inverse map.  y[N], logabsdet[N]; bin_dev[N] (may be NULL) = selected bin, -1 in the tails.
- * min_bin_width = min_bin_height = min_derivative = 1e-3 as in the reference. */
+ * min_bin_width = min_bin_height = min_derivative = 1e-3 as in the reference.
+ * K: 1 .. WF_RQS_MAX_BINS (159).  K in {4, 8, 16, 32} with 16-byte aligned uw / uh runs from registers; every other K (and those
+ * four behind an unaligned uw or uh) stages a [256][K + 1] fp32 tile in LDS, which at K = 159 is the whole 160 KiB of a CU.
+ * K in 160 .. 256 is valid in the reference and not built here: WF_ERR_UNSUPPORTED, returned before any device call, outputs
+ * untouched.  K > 256 (or 1e-3 K > 1): WF_ERR_INVALID. */
 int wf_rqs_fwd(const float* x_dev, const float* uw_dev, const float* uh_dev, const float* ud_dev, int64_t N, int32_t K,
                int32_t n_deriv, int32_t inverse, float left, float right, float bottom, float top, float* y_dev,
                float* logabsdet_dev, int32_t* bin_dev, void* stream);

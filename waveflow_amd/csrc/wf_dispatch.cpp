@@ -620,6 +620,8 @@ int wf_rqs_fwd(const float* x_dev, const float* uw_dev, const float* uh_dev, con
                int32_t inverse, float left, float right, float bottom, float top, float* y_dev, float* logabsdet_dev, int32_t* bin_dev,
                void* stream) {
     if (N < 0 || K < 1 || K > 256) return WF_ERR_INVALID;
+    // the staged kernel keeps a [256][K + 1] fp32 tile in LDS: 160 KiB per CU holds K <= 159.  Refused here, before any device call.
+    if (K > WF_RQS_MAX_BINS) return WF_ERR_UNSUPPORTED;
     if (n_deriv != K - 1 && n_deriv != K + 1) return WF_ERR_INVALID;
     if (!(right > left) || !(top > bottom)) return WF_ERR_INVALID;
     if (1e-3f * K > 1.0f) return WF_ERR_INVALID;   // "Minimal bin width too large for the number of bins" (neural_splines.py:91-94)

@@ -648,6 +648,7 @@ int launch_nsc_model(const NscModelDev& md, int mode, const float* x, int64_t B,
 
 int launch_rqs(const float* x, const float* uw, const float* uh, const float* ud, int64_t N, int K, int n_deriv, int inverse, float left,
                float right, float bottom, float top, float* y, float* ld, int32_t* bin, void* stream) {
+    if (K > WF_RQS_MAX_BINS) return WF_ERR_UNSUPPORTED;   // the [256][K + 1] tile below would not fit the 160 KiB of a CU
     if (N == 0) return WF_OK;
     const bool aligned = ((((uintptr_t)uw) | ((uintptr_t)uh)) & 15) == 0;
     if (aligned) {
