@@ -599,6 +599,34 @@ class DeviceModel:
         _lib.check(dmc.lib().wf_vqmc_dmc_step(self._h, ctypes.byref(state.c), int(seed) & 0xFFFFFFFFFFFFFFFF, state.n, *self._protons(protons), tau,
                                               int(bool(limit_drift)), e_cut, *ws, self._stream()), "wf_vqmc_dmc_step")
 
+    # ---- forward walking behind the comb (include/waveflow_dmc_observe.h; dmc.run(..., forward_walk=) drives it)
+    def make_forward_walk(self, n_walkers, n_slots, stride, n_density_bins=200, n_pair_bins=200, lo=None, hi=None, series_len=4096):
+        """-> dmc_observables.ForwardWalk for a population of n_walkers on this model's device; lo, hi default to the model's box."""
+        from . import dmc_observables
+        lo = -float(self.desc.box_size) if lo is None else lo
+        hi = float(self.desc.box_size) if hi is None else hi
+        return dmc_observables.ForwardWalk(n_walkers, self.D, n_slots, stride, n_density_bins, n_pair_bins, lo, hi, series_len, f"cuda:{self.device}")
+
+    def dmc_fw_workspace_bytes(self, n_walkers, n_slots):
+        """Workspace of dmc_fw_step for a population of n_walkers and a tracker of n_slots; WfError as dmc_workspace_bytes."""
+        from . import dmc_observables
+        return _lib.check(dmc_observables.lib().wf_vqmc_dmc_fw_workspace_bytes(self._h, int(n_walkers), int(n_slots)), "wf_vqmc_dmc_fw_workspace_bytes")
+
+    def dmc_fw_step(self, state, fw, seed, protons, tau, limit_drift=False, e_cut=0.0):
+        """One DMC generation with its forward-walking update (wf_vqmc_dmc_fw_step): the launches of dmc_step -- the state it leaves is bit for
+        bit the one dmc_step leaves -- then the tracker `fw` (a ForwardWalk) composed with the comb's parent indices, measured and retagged as
+        the state's counter says.  No host work, no wait, capturable like dmc_step.  Arguments are checked before anything is launched."""
+        from . import dmc, dmc_observables
+        tau, e_cut = dmc._check_tau(tau, e_cut)
+        if state.D != self.D:
+            raise ValueError(f"the state holds {state.D} columns, the model has {self.D}")
+        if not isinstance(fw, dmc_observables.ForwardWalk) or (fw.n, fw.D) != (state.n, state.D) or fw.device != state.device:
+            raise ValueError(f"the tracker must be a ForwardWalk of {state.n} walkers of {state.D} coordinates on {state.device}")
+        ws = self._train_ws(state.st, self.dmc_fw_workspace_bytes(state.n, fw.n_slots))
+        _lib.check(dmc_observables.lib().wf_vqmc_dmc_fw_step(self._h, ctypes.byref(state.c), ctypes.byref(fw.c), int(seed) & 0xFFFFFFFFFFFFFFFF, state.n,
+                                                             *self._protons(protons), tau, int(bool(limit_drift)), e_cut, *ws, self._stream()),
+                   "wf_vqmc_dmc_fw_step")
+
     def block_sums(self, v):
         """fp64 [sum v, sum v^2, count] on the device (deterministic order)."""
         torch = _torch()

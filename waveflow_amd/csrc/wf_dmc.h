@@ -64,4 +64,14 @@ int launch_dmc_trial_from_record(const double* record, double* e_trial, void* st
 // the step's last launch: ring record, E_T, counter
 int launch_dmc_finish(const wf_dmc_state* st, const double* record, int64_t B, double tau, void* stream);
 
+// ---- wf_train_dmc.cpp: the generation, shared by wf_vqmc_dmc_step and wf_vqmc_dmc_fw_step (wf_train_dmc_observe.cpp)
+// what wf_vqmc_dmc_workspace_bytes returns
+int64_t dmc_step_bytes(const wf_model* m, int64_t batch);
+// the refusals of wf_vqmc_dmc_step in its order, short of the workspace; fills *pr
+int dmc_step_check(const wf_model* m, const wf_dmc_state* st, int64_t batch, const float* protons_host, int n_protons, double tau, double e_cut,
+                   Protons* pr);
+// the launches of one generation behind those checks, in a workspace of dmc_step_bytes; src_out (optional): the comb's parent indices [batch]
+int dmc_step_launch(const wf_model* m, const wf_dmc_state* st, uint64_t seed, int64_t batch, const Protons& pr, double tau, int limit_drift,
+                    double e_cut, int32_t* src_out, void* workspace_dev, void* stream);
+
 }  // namespace wf

@@ -59,12 +59,54 @@ bool state_complete(const wf_dmc_state* st) {
 
 }  // namespace
 
-extern "C" {
+// ---- what wf_vqmc_dmc_step and wf_vqmc_dmc_fw_step (wf_train_dmc_observe.cpp) share (wf_dmc.h)
+namespace wf {
 
-int64_t wf_vqmc_dmc_workspace_bytes(const wf_model* m, int64_t batch) {
+int64_t dmc_step_bytes(const wf_model* m, int64_t batch) {
     if (!m || batch < 1) return WF_ERR_INVALID;
     if (!dmc_model_covered(m) || !dmc_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
     return dmc_step_layout(m, batch).total;
+}
+
+int dmc_step_check(const wf_model* m, const wf_dmc_state* st, int64_t batch, const float* protons_host, int n_protons, double tau, double e_cut,
+                   Protons* pr) {
+    if (!m || batch < 1 || !state_complete(st) || !make_protons(protons_host, n_protons, pr)) return WF_ERR_INVALID;
+    if (!std::isfinite(tau) || !(tau > 0.0) || !std::isfinite(e_cut) || e_cut < 0.0) return WF_ERR_INVALID;
+    if (!dmc_model_covered(m) || !dmc_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
+    if (!m->params_set) return WF_ERR_INVALID;
+    return WF_OK;
+}
+
+int dmc_step_launch(const wf_model* m, const wf_dmc_state* st, uint64_t seed, int64_t batch, const Protons& pr, double tau, int limit_drift,
+                    double e_cut, int32_t* src_out, void* workspace_dev, void* stream) {
+    const DmcStepLayout l = dmc_step_layout(m, batch);
+    DeviceGuard g(m->device);
+    const int D = m->desc.n_dim;
+    char* w = (char*)workspace_dev;
+    float *xn = (float*)(w + l.x), *psn = (float*)(w + l.psi), *grn = (float*)(w + l.grad), *hdn = (float*)(w + l.hdiag);
+    int32_t* flag = (int32_t*)(w + l.flag);
+    double *wt = (double*)(w + l.w), *record = (double*)(w + l.record);
+    const DmcParams p{tau, std::sqrt(tau), e_cut, m->desc.box_size, limit_drift != 0, (unsigned long long)seed, 0ull,
+                      (const unsigned long long*)st->counter_dev};
+    int rc = launch_dmc_propose(st->x_dev, st->psi_dev, st->grad_dev, batch, D, p, xn, flag, nullptr, stream);
+    if (rc) return rc;
+    rc = wf_psi_coord_derivs(m, xn, batch, psn, grn, hdn, stream);
+    if (rc) return rc;
+    rc = launch_dmc_accept(st->x_dev, st->psi_dev, st->grad_dev, st->e_loc_dev, xn, psn, grn, hdn, flag, batch, D, pr, p, st->e_trial_dev, wt, record,
+                           nullptr, nullptr, nullptr, 0, w + l.partials, stream);
+    if (rc) return rc;
+    rc = launch_dmc_reconfigure(st->x_dev, st->psi_dev, st->grad_dev, st->e_loc_dev, wt, batch, D, p, 2, src_out, nullptr,
+                                (unsigned long long*)st->status_dev, w + l.comb, stream);
+    if (rc) return rc;
+    return launch_dmc_finish(st, record, batch, tau, stream);
+}
+
+}  // namespace wf
+
+extern "C" {
+
+int64_t wf_vqmc_dmc_workspace_bytes(const wf_model* m, int64_t batch) {
+    return dmc_step_bytes(m, batch);
 }
 
 int wf_vqmc_dmc_init(const wf_model* m, const wf_dmc_state* st, uint64_t seed, int64_t batch, const float* protons_host, int32_t n_protons,
@@ -104,31 +146,10 @@ int wf_vqmc_dmc_init(const wf_model* m, const wf_dmc_state* st, uint64_t seed, i
 int wf_vqmc_dmc_step(const wf_model* m, const wf_dmc_state* st, uint64_t seed, int64_t batch, const float* protons_host, int32_t n_protons,
                      double tau, int32_t limit_drift, double e_cut, void* workspace_dev, int64_t workspace_bytes, void* stream) {
     Protons pr{};
-    if (!m || batch < 1 || !state_complete(st) || !make_protons(protons_host, n_protons, &pr)) return WF_ERR_INVALID;
-    if (!std::isfinite(tau) || !(tau > 0.0) || !std::isfinite(e_cut) || e_cut < 0.0) return WF_ERR_INVALID;
-    if (!dmc_model_covered(m) || !dmc_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
-    if (!m->params_set || !workspace_dev) return WF_ERR_INVALID;
-    const DmcStepLayout l = dmc_step_layout(m, batch);
-    if (workspace_bytes < l.total) return WF_ERR_INVALID;
-    DeviceGuard g(m->device);
-    const int D = m->desc.n_dim;
-    char* w = (char*)workspace_dev;
-    float *xn = (float*)(w + l.x), *psn = (float*)(w + l.psi), *grn = (float*)(w + l.grad), *hdn = (float*)(w + l.hdiag);
-    int32_t* flag = (int32_t*)(w + l.flag);
-    double *wt = (double*)(w + l.w), *record = (double*)(w + l.record);
-    const DmcParams p{tau, std::sqrt(tau), e_cut, m->desc.box_size, limit_drift != 0, (unsigned long long)seed, 0ull,
-                      (const unsigned long long*)st->counter_dev};
-    int rc = launch_dmc_propose(st->x_dev, st->psi_dev, st->grad_dev, batch, D, p, xn, flag, nullptr, stream);
+    const int rc = dmc_step_check(m, st, batch, protons_host, n_protons, tau, e_cut, &pr);
     if (rc) return rc;
-    rc = wf_psi_coord_derivs(m, xn, batch, psn, grn, hdn, stream);
-    if (rc) return rc;
-    rc = launch_dmc_accept(st->x_dev, st->psi_dev, st->grad_dev, st->e_loc_dev, xn, psn, grn, hdn, flag, batch, D, pr, p, st->e_trial_dev, wt, record,
-                           nullptr, nullptr, nullptr, 0, w + l.partials, stream);
-    if (rc) return rc;
-    rc = launch_dmc_reconfigure(st->x_dev, st->psi_dev, st->grad_dev, st->e_loc_dev, wt, batch, D, p, 2, nullptr, nullptr,
-                                (unsigned long long*)st->status_dev, w + l.comb, stream);
-    if (rc) return rc;
-    return launch_dmc_finish(st, record, batch, tau, stream);
+    if (!workspace_dev || workspace_bytes < dmc_step_layout(m, batch).total) return WF_ERR_INVALID;
+    return dmc_step_launch(m, st, seed, batch, pr, tau, limit_drift, e_cut, nullptr, workspace_dev, stream);
 }
 
 }  // extern "C"

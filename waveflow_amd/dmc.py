@@ -304,7 +304,8 @@ def _check_run(n_walkers, tau, n_steps, n_equil, e_cut, n_blocks):
     return n_walkers, tau, n_steps, n_equil, e_cut, n_blocks
 
 
-def run(model, protons, n_walkers, tau, n_steps, n_equil, seed, exact_sampler=True, limit_drift=False, e_cut=0.0, use_graph=True, n_blocks=20):
+def run(model, protons, n_walkers, tau, n_steps, n_equil, seed, exact_sampler=True, limit_drift=False, e_cut=0.0, use_graph=True, n_blocks=20,
+        forward_walk=None):
     """A fixed-node DMC run: `n_walkers` walkers from |psi|^2 (DeviceModel.dmc_init), n_equil generations that are
     discarded, then n_steps measured ones (DeviceModel.dmc_step).  With use_graph the step is captured once (vqmc.capture_step; its warm-up
     call outside the capture is undone) and replayed; the host waits once, at the end.  -> dict:
@@ -313,28 +314,47 @@ def run(model, protons, n_walkers, tau, n_steps, n_equil, seed, exact_sampler=Tr
       acceptance          accepted moves / moves over the measured generations
       left_domain, not_finite   moves rejected for leaving the domain / for a value that is not finite (measured generations)
       status              combs that found no usable weight (0 in a healthy run);  generations: the device's counter;  ring: every record.
-    tau * n_equil below 30 a.u. draws a RuntimeWarning (the He decay time is 5.7 a.u.); the run goes on."""
+    tau * n_equil below 30 a.u. draws a RuntimeWarning (the He decay time is 5.7 a.u.); the run goes on.
+    forward_walk: a dmc_observables.ForwardWalk for this population (model.make_forward_walk), or None.  With one, every generation is
+    DeviceModel.dmc_fw_step (the same walk, bit for bit), the tracker's accumulators are zeroed behind the equilibration, and the dict gains
+    "forward_walk": dmc_observables.result(forward_walk, n_blocks) -- per lag V_en, V_ee with blocking errors, densities, the pair distribution
+    and the surviving share of ancestors.  n_slots * stride * tau below the decay time draws a RuntimeWarning."""
     import torch
     n_walkers, tau, n_steps, n_equil, e_cut, n_blocks = _check_run(n_walkers, tau, n_steps, n_equil, e_cut, n_blocks)
+    fw = forward_walk
+    if fw is not None:
+        from . import dmc_observables
+        if not isinstance(fw, dmc_observables.ForwardWalk) or fw.n != n_walkers:
+            raise ValueError(f"forward_walk must be a ForwardWalk of {n_walkers} walkers")
+        dmc_observables.warn_if_short(fw.n_slots, fw.stride, tau)
     total = n_equil + n_steps
     state = model.make_dmc_state(n_walkers, ring_len=total)
-    state.st["ws"] = model._workspace(model.dmc_workspace_bytes(n_walkers), state.device)   # allocated here, outside the capture
+    nbytes = model.dmc_workspace_bytes(n_walkers) if fw is None else model.dmc_fw_workspace_bytes(n_walkers, fw.n_slots)
+    state.st["ws"] = model._workspace(nbytes, state.device)   # allocated here, outside the capture
     model.dmc_init(state, seed, protons, exact_sampler=exact_sampler)
+    if fw is not None:
+        fw.reset()
 
     def step():
-        model.dmc_step(state, seed, protons, tau, limit_drift=limit_drift, e_cut=e_cut)
+        if fw is None:
+            model.dmc_step(state, seed, protons, tau, limit_drift=limit_drift, e_cut=e_cut)
+        else:
+            model.dmc_fw_step(state, fw, seed, protons, tau, limit_drift=limit_drift, e_cut=e_cut)
     launch = step
     if use_graph:
         from . import vqmc
-        kept = [t.clone() for t in state.tensors()]
+        held = state.tensors() + (fw.tensors() if fw is not None else ())
+        kept = [t.clone() for t in held]
 
         def warm_up():
             # one step outside the capture (the derivative entry grows the model's scratch there, not inside); what it did is taken back
             step()
-            for t, k in zip(state.tensors(), kept):
+            for t, k in zip(held, kept):
                 t.copy_(k)
         launch = vqmc.capture_step(model, step, warm_up, "hipGraph capture of the DMC step failed")
-    for _ in range(total):
+    for i in range(total):
+        if fw is not None and i == n_equil:
+            fw.zero_accumulators()       # (on the stream, between two generations: the tags and the genealogy stay)
         launch()
     torch.cuda.synchronize(state.device)
     ring = state.ring.cpu().numpy()
@@ -343,6 +363,7 @@ def run(model, protons, n_walkers, tau, n_steps, n_equil, seed, exact_sampler=Tr
     e_dmc, e_err = blocked_mean(e_mixed, n_blocks)
     g_mean, g_err = blocked_mean(e_growth, n_blocks)
     moves = float(n_walkers) * n_steps
-    return {"e_mixed": e_mixed, "e_growth": e_growth, "e_dmc": e_dmc, "e_dmc_stderr": e_err, "e_growth_mean": g_mean, "e_growth_stderr": g_err,
+    extra = {"forward_walk": dmc_observables.result(fw, n_blocks)} if fw is not None else {}
+    return {**extra, "e_mixed": e_mixed, "e_growth": e_growth, "e_dmc": e_dmc, "e_dmc_stderr": e_err, "e_growth_mean": g_mean, "e_growth_stderr": g_err,
             "acceptance": float(rec[:, 3].sum() / moves), "left_domain": int(rec[:, 4].sum()), "not_finite": int(rec[:, 5].sum()),
             "status": int(state.status.item()), "generations": int(state.counter.item()), "ring": ring, "state": state}
