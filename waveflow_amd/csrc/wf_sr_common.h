@@ -1,4 +1,4 @@
-// wf_sr_common.h -- what wf_kernels_sr.hip, wf_kernels_sr_step.hip and wf_kernels_sr_spring.hip share: the launch check, the block sum, the
+// wf_sr_common.h -- what wf_kernels_sr.hip, wf_kernels_sr_step.hip, wf_kernels_sr_spring.hip and wf_kernels_sr_cg.hip share: the launch check, the block sum, the
 // predicated 4-column load of the rows, the test for 16-byte loads, the slab pass of the apply (defined in wf_kernels_sr.hip, launched from
 // there and from wf_kernels_sr_spring.hip) and the workspace it needs.
 #pragma once

@@ -1,7 +1,9 @@
 """Stochastic reconfiguration (the natural gradient of variational Monte Carlo) from per-walker Jacobian rows, in its B x B ("minSR") form:
 the ctypes surface of include/waveflow_sr.h, and of include/waveflow_sr_step.h (the whole training step on the device: STEP_PROTOTYPES,
 SrTrainState; core.DeviceModel.sr_step drives it), and of include/waveflow_sr_spring.h (the SPRING optimiser: SPRING_PROTOTYPES, SpringTrainState,
-`matvec`, `apply_add`, `spring_rhs`, `clip_local_energies`, `spring_direction`; core.DeviceModel.spring_step drives the whole step).
+`matvec`, `apply_add`, `spring_rhs`, `clip_local_energies`, `spring_direction`; core.DeviceModel.spring_step drives the whole step), and of
+include/waveflow_sr_cg.h (the same solve without the B x B matrix, for more than MAX_WALKERS walkers: CG_PROTOTYPES, `solve_cg`, `cg_reference`,
+and `solver='cg'` of `natural_gradient` and `spring_direction`).
 
 With O[b][k] = d ln psi_b / d theta_k, local energies e, H = I - 1 1^T / B and lambda > 0,
     d = (O^T H O / B + lambda I)^-1 (2 / B) O^T H e  =  (2 / B) O^T H y,    (H O O^T H / B + lambda I) y = H e
@@ -54,6 +56,14 @@ SPRING_PROTOTYPES = {
                             + _ws + [_vp]),
 }
 
+# name -> (restype, argtypes): every function of include/waveflow_sr_cg.h, in its order (tests/test_sr_cg_host.py)
+CG_PROTOTYPES = {
+    "wf_sr_cg_workspace_bytes": (_i64, [_i64, _i64]),
+    "wf_sr_cg_solve": (_i32, [_vp, _i64, _i64, _i64, _vp, _f64, _f64, _f64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp] + _ws + [_vp]),
+}
+MAX_ROWS = 65536     # the row passes (wf_sr_matvec, wf_sr_apply, wf_sr_cg_solve)
+SOLVERS = ('cholesky', 'cg')
+
 _bound = None
 
 
@@ -65,12 +75,31 @@ class NotPositiveDefinite(ArithmeticError):
         super().__init__(f"stochastic reconfiguration: pivot {self.pivot} of the shifted B x B matrix is not positive (more damping, or non-finite rows)")
 
 
+class NotConverged(ArithmeticError):
+    """solve_cg used its `max_iter` iterations; `iterations` and `residual` (the recurrence's |r| / |rhs|) say where it stood."""
+
+    def __init__(self, iterations, residual, tol):
+        self.iterations, self.residual = int(iterations), float(residual)
+        super().__init__(f"stochastic reconfiguration: conjugate gradients stood at |r| / |rhs| = {self.residual:.3e} after {self.iterations} "
+                         f"iterations (tol {tol:.1e}): more iterations or more damping")
+
+
+class NotFinite(ArithmeticError):
+    """solve_cg met a value that is not finite (rows, right-hand side), a shift that is not positive, or p^T A p <= 0; y is NaN."""
+
+    def __init__(self, iterations):
+        self.iterations = int(iterations)
+        super().__init__(f"stochastic reconfiguration: conjugate gradients broke down in iteration {self.iterations + 1} (rows or right-hand side "
+                         "that are not finite, or a shift that is not positive)")
+
+
 def lib():
-    """The handle of _lib.lib() with PROTOTYPES, STEP_PROTOTYPES and SPRING_PROTOTYPES applied to it."""
+    """The handle of _lib.lib() with PROTOTYPES, STEP_PROTOTYPES, SPRING_PROTOTYPES and CG_PROTOTYPES applied to it."""
     global _bound
     L = _lib.lib()
     if _bound is not L:
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(STEP_PROTOTYPES.items()) + list(SPRING_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(STEP_PROTOTYPES.items()) + list(SPRING_PROTOTYPES.items()) + list(
+                CG_PROTOTYPES.items()):
             f = getattr(L, name)
             f.restype = restype
             f.argtypes = argtypes
@@ -121,6 +150,20 @@ def _check_spring(momentum, norm_constraint, clip):
     if not clip >= 0.0:
         raise ValueError(f"the clip factor must be >= 0 (0: no clipping), got {clip}")
     return momentum, norm_constraint, clip
+
+
+def _check_solver(solver, tol=1e-8, max_iter=2000, round_iters=32):
+    """-> (solver, tol, max_iter, round_iters)"""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    tol = float(tol)
+    if not 0.0 < tol < 1.0:
+        raise ValueError(f"tol must lie in (0, 1), got {tol}")
+    if int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"max_iter must be a whole number >= 1, got {max_iter}")
+    if int(round_iters) != round_iters or int(round_iters) < 1:
+        raise ValueError(f"round_iters must be a whole number >= 1, got {round_iters}")
+    return solver, tol, int(max_iter), int(round_iters)
 
 
 def _check_rows(rows, limit=None):
@@ -228,14 +271,21 @@ def apply(rows, y, scale, workspace=None):
     return _apply(rows, B, P, ld, y.contiguous(), scale, workspace if workspace is not None else _workspace(B, P, rows.device))
 
 
-def natural_gradient(rows, e_loc, damping=0.0, relative_damping=1e-3):
+def natural_gradient(rows, e_loc, damping=0.0, relative_damping=1e-3, solver='cholesky', tol=1e-8, max_iter=2000):
     """d = (S + lambda I)^-1 g for rows O = d ln psi / d theta [B, P] and local energies e_loc [B]: S = O^T H O / B, g = (2 / B) O^T H e,
     lambda = damping + relative_damping * trace(Tbar) / B -> float32 cuda [P].  Three library calls on the current stream, then one read of the
-    solver's status: NotPositiveDefinite if a pivot was not positive."""
+    solver's status: NotPositiveDefinite if a pivot was not positive.  solver='cg': Tbar is never formed and B may exceed MAX_WALKERS -- solve_cg
+    to `tol` within `max_iter` iterations (NotConverged, NotFinite), then the same apply."""
     import torch
     damping, relative_damping = _check_damping(damping, relative_damping)
-    B, P, ld = _check_rows(rows, limit=MAX_WALKERS)
+    solver, tol, max_iter, _ = _check_solver(solver, tol, max_iter)
+    B, P, ld = _check_rows(rows, limit=MAX_WALKERS if solver == 'cholesky' else MAX_ROWS)
     _check_vector(e_loc, B, None, "e_loc", rows.device)
+    if solver == 'cg':
+        ws = _cg_workspace(B, P, rows.device)
+        e = e_loc.double()
+        y, _ = _solve_cg(rows, B, P, ld, e - e.mean(), damping, relative_damping, tol, max_iter, 32, False, ws)
+        return _apply(rows, B, P, ld, y, 2.0 / B, ws)
     ws = _workspace(B, P, rows.device)
     T = _gram(rows, B, P, ld, ws)
     e = e_loc.double()
@@ -338,22 +388,26 @@ def clip_local_energies(e_loc, clip):
     return torch.minimum(torch.maximum(e, c - float(clip) * w), c + float(clip) * w)
 
 
-def spring_direction(rows, e_loc, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0):
+def spring_direction(rows, e_loc, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0, solver='cholesky', tol=1e-8, max_iter=2000):
     """The SPRING direction d = mu prev + (2 / B) O^T H y with (Tbar + lambda I) y = H (e~ - (mu / 2) O prev), the minimiser of
     (1 / B) |H O d - 2 H e~|^2 + lambda |d - mu prev|^2; e~ = clip_local_energies(e_loc, clip); momentum 0 gives natural_gradient.
     rows [B, P] float32 cuda, e_loc [B], prev float32 cuda [P] (the previous d; zeros at the start) -> float32 cuda [P].  Library calls on the
-    current stream, then one read of the solver's status: NotPositiveDefinite if a pivot was not positive."""
+    current stream, then one read of the solver's status: NotPositiveDefinite if a pivot was not positive.  solver='cg': as in natural_gradient."""
     import torch
     damping, relative_damping = _check_damping(damping, relative_damping)
     momentum, _, clip = _check_spring(momentum, 0.0, clip)
-    B, P, ld = _check_rows(rows, limit=MAX_WALKERS)
+    solver, tol, max_iter, _ = _check_solver(solver, tol, max_iter)
+    B, P, ld = _check_rows(rows, limit=MAX_WALKERS if solver == 'cholesky' else MAX_ROWS)
     _check_vector(e_loc, B, None, "e_loc", rows.device)
     _check_vector(prev, P, torch.float32, "prev", rows.device)
     prev = prev.contiguous()
-    ws = _workspace(B, P, rows.device)
+    ws = _workspace(B, P, rows.device) if solver == 'cholesky' else _cg_workspace(B, P, rows.device)
     r = clip_local_energies(e_loc, clip)
     if momentum != 0.0:
         r = r - (0.5 * momentum) * _matvec(rows, B, P, ld, prev)
+    if solver == 'cg':
+        y, _ = _solve_cg(rows, B, P, ld, r - r.mean(), damping, relative_damping, tol, max_iter, 32, False, ws)
+        return _apply_add(rows, B, P, ld, y, 2.0 / B, prev, momentum, torch.empty(P, dtype=torch.float32, device=rows.device), ws)
     T = _gram(rows, B, P, ld, ws)
     y, info = _solve(T, B, r - r.mean(), damping, relative_damping, ws)
     d = _apply_add(rows, B, P, ld, y, 2.0 / B, prev, momentum, torch.empty(P, dtype=torch.float32, device=rows.device), ws)
@@ -361,3 +415,107 @@ def spring_direction(rows, e_loc, prev, momentum, damping=0.0, relative_damping=
     if pivot != 0:
         raise NotPositiveDefinite(pivot)
     return d
+
+
+# ---- the matrix-free solve (include/waveflow_sr_cg.h)
+
+def _cg_workspace(B, P, device):
+    from .core import DeviceModel
+    nbytes = _lib.check(lib().wf_sr_cg_workspace_bytes(B, P), "wf_sr_cg_workspace_bytes")
+    return DeviceModel._workspace(nbytes, device)   # (at least wf_sr_apply's: the apply behind the solve uses it too)
+
+
+def _cg_call(rows, B, P, ld, rhs, damping, relative_damping, tol, n_iter, restart, precondition, y, info, ws):
+    """One wf_sr_cg_solve on the current stream: nothing waits, nothing is allocated (capturable)."""
+    import torch
+    with torch.cuda.device(rows.device):
+        _lib.check(lib().wf_sr_cg_solve(rows.data_ptr(), B, P, ld, rhs.data_ptr(), damping, relative_damping, tol, int(n_iter), int(bool(restart)),
+                                        int(bool(precondition)), y.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        _lib.stream_ptr(rows.device)), "wf_sr_cg_solve")
+
+
+def _solve_cg(rows, B, P, ld, rhs, damping, relative_damping, tol, max_iter, round_iters, precondition, ws):
+    import torch
+    y = torch.empty(B, dtype=torch.float64, device=rows.device)
+    info = torch.empty(4, dtype=torch.float64, device=rows.device)
+    rhs = rhs.contiguous()
+    done, restart = 0, True
+    while True:
+        n = min(round_iters, max_iter - done)
+        _cg_call(rows, B, P, ld, rhs, damping, relative_damping, tol, n, restart, precondition, y, info, ws)
+        done, restart = done + n, False
+        status, iterations, residual, _ = info.cpu().tolist()   # (the round's one wait)
+        if status == 0.0:
+            return y, info
+        if status != 1.0:
+            raise NotFinite(iterations)
+        if done >= max_iter:
+            raise NotConverged(iterations, residual, tol)
+
+
+def solve_cg(rows, rhs, damping=0.0, relative_damping=1e-3, tol=1e-8, max_iter=2000, round_iters=32, precondition=False, workspace=None):
+    """(Tbar + lambda I) y = rhs without Tbar: conjugate gradients, each iteration one O^T (H p) pass and one O z pass over the rows (wf_sr_cg_solve)
+    -> (y float64 cuda [B], info float64 cuda [4] = status 0, iterations, the recurrence's |r| / |rhs|, lambda).  rows float32 cuda [B, P] with
+    B up to MAX_ROWS, rhs float64 cuda [B], already centred; lambda = damping + relative_damping * trace(Tbar) / B as in `solve`;
+    precondition: Jacobi, with the diagonal of Tbar + lambda I -- off by default, and off in natural_gradient / spring_direction: on He's rows
+    it costs 9 to 30 times the iterations (Tbar + lambda I is a few large eigenvalues over a cluster at lambda, which plain
+    conjugate gradients resolve in tens of steps and which scaling by rows of very different norms takes apart).  Rounds of `round_iters` iterations are enqueued and `info` is read between
+    them (one wait per round); NotFinite on status 2, NotConverged when `max_iter` iterations did not reach |r| <= tol |rhs|."""
+    import torch
+    damping, relative_damping = _check_damping(damping, relative_damping)
+    _, tol, max_iter, round_iters = _check_solver('cg', tol, max_iter, round_iters)
+    B, P, ld = _check_rows(rows, limit=MAX_ROWS)
+    _check_vector(rhs, B, torch.float64, "rhs", rows.device)
+    return _solve_cg(rows, B, P, ld, rhs, damping, relative_damping, tol, max_iter, round_iters, precondition,
+                     workspace if workspace is not None else _cg_workspace(B, P, rows.device))
+
+
+def cg_reference(rows, rhs, damping=0.0, relative_damping=1e-3, tol=1e-8, max_iter=2000, precondition=False, history=False):
+    """The recurrences of wf_sr_cg_solve in NumPy float64 (sums in NumPy's order, not the device's): rows [B, P] and rhs [B] array-likes
+    -> (y float64 [B], info float64 [4] = status, iterations, the recurrence's |r| / |rhs|, lambda); status 1 when `max_iter` iterations did
+    not converge.  history=True adds a third result, the list of (recursive, true) relative residuals after every iteration."""
+    import numpy as np
+    O = np.asarray(rows, dtype=np.float64)
+    rhs = np.asarray(rhs, dtype=np.float64)
+    B = O.shape[0]
+    nan = float("nan")
+    obar = O.sum(0) / B
+    diag = ((O - obar) ** 2).sum(1) / B                         # the diagonal of Tbar = H O O^T H / B
+    lam = float(damping) + float(relative_damping) * diag.sum() / B
+    rhs2 = float(rhs @ rhs)
+    steps = []
+    out = (lambda y, status, it, r2: (y, np.array([status, it, np.sqrt(r2 / rhs2) if rhs2 > 0 else (nan if status == 2 else 0.0), lam]))
+           + ((steps,) if history else ()))
+    if not (np.isfinite(diag.sum()) and np.isfinite(rhs2) and np.isfinite(lam) and lam > 0.0):
+        return out(np.full(B, nan), 2, 0, nan)
+    if rhs2 == 0.0 or B == 1:
+        return out(rhs / lam, 0, 0, 0.0)
+    M = diag + lam if precondition else np.ones(B)
+
+    def tbar(v):
+        z = O.T @ (v - v.mean())                                # pass A
+        q = O @ z                                               # pass B
+        return (q - q.mean()) / B, float(z @ z)
+    y, r = np.zeros(B), rhs.copy()
+    p = r / M
+    rho = float(r @ p)
+    r2 = rhs2
+    for it in range(1, int(max_iter) + 1):
+        tp, zz = tbar(p)
+        pAp = zz / B + lam * float(p @ p)
+        if not (np.isfinite(pAp) and pAp > 0.0):
+            return out(np.full(B, nan), 2, it - 1, r2)
+        alpha = rho / pAp
+        y = y + alpha * p
+        r = r - alpha * (tp + lam * p)
+        r2, rz = float(r @ r), float(r @ (r / M))
+        if history:
+            true = rhs - (tbar(y)[0] + lam * y)
+            steps.append((np.sqrt(r2 / rhs2), np.sqrt(float(true @ true) / rhs2)))
+        if not (np.isfinite(r2) and np.isfinite(rz)):
+            return out(np.full(B, nan), 2, it, r2)
+        if r2 <= tol * tol * rhs2:
+            return out(y, 0, it, r2)
+        p = r / M + (rz / rho) * p
+        rho = rz
+    return out(y, 1, int(max_iter), r2)

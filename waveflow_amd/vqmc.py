@@ -254,25 +254,32 @@ def log_psi_jacobian(psi):
     return jac
 
 
-def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=1e-3, group=None):
+def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=1e-3, group=None, solver='cholesky', tol=1e-8, max_iter=2000):
     """Stochastic reconfiguration on the walkers of `batch`: d = (S + lambda I)^-1 g with O_k(x_b) = d ln psi_b / d theta_k (the rows of
     log_psi_jacobian, written once with the weight 1 / (psi + 1e-8)), S = O^T H O / B, g = (2 / B) O^T H e_loc, e_loc = H psi / (psi + 1e-8)
     and lambda = damping + relative_damping * trace(H O O^T H / B) / B, solved in its B x B form (waveflow_amd.sr).
-    -> (d float32 cuda [n_params], loss = mean e_loc).  Sharded walkers (`group`) are not supported."""
+    -> (d float32 cuda [n_params], loss = mean e_loc).  Sharded walkers (`group`) are not supported.  solver='cg' (with tol, max_iter): the
+    matrix-free solve of sr.solve_cg, for batches beyond sr.MAX_WALKERS."""
     from . import sr
     if group is not None:
         raise NotImplementedError("stochastic reconfiguration over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
     sr._check_damping(damping, relative_damping)
+    sr._check_solver(solver, tol, max_iter)
     model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
     inv = 1.0 / (ps + 1e-8)
     e_loc = hpsi * inv
     rows = model.psi_jacobian(x, w_psi=inv)
-    d = sr.natural_gradient(rows, e_loc, damping=damping, relative_damping=relative_damping)
+    d = sr.natural_gradient(rows, e_loc, damping=damping, relative_damping=relative_damping, **_solver_args(solver, tol, max_iter))
     return d, float(e_loc.double().mean())
 
 
+def _solver_args(solver, tol, max_iter):
+    """The solver keywords for sr.natural_gradient / sr.spring_direction: none for the dense solve, whose call stays as it was."""
+    return {} if solver == 'cholesky' else {"solver": solver, "tol": tol, "max_iter": max_iter}
+
+
 def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **damping):
-    """One stochastic-reconfiguration step theta <- theta - lr d (sr_natural_gradient; `damping`: its damping / relative_damping;
+    """One stochastic-reconfiguration step theta <- theta - lr d (sr_natural_gradient; `damping`: its damping / relative_damping, and solver / tol / max_iter;
     learning_rate: a number, or a schedule called with `epoch`) -> (new params, loss).  `params` is left as it is: the result is a new
     pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one."""
     d, loss_val = sr_natural_gradient(params, psi, h_fn, batch, group=group, **damping)
@@ -283,21 +290,24 @@ def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **
     return checkpoint.unflatten_like(params, flat - np.float32(lr) * d.cpu().numpy()), loss_val
 
 
-def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0, group=None):
+def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0, group=None, solver='cholesky', tol=1e-8,
+                     max_iter=2000):
     """The SPRING direction on the walkers of `batch` (sr.spring_direction on the rows and local energies of sr_natural_gradient): stochastic
     reconfiguration pulled towards momentum * prev, local energies clamped `clip` mean absolute deviations around their median (0: not clamped).
     prev: the previous direction, float32 cuda [n_params] (zeros at the start).  -> (d float32 cuda [n_params], loss = mean of the unclipped e_loc).
-    Sharded walkers (`group`) are not supported."""
+    Sharded walkers (`group`) are not supported.  solver, tol, max_iter: as in sr_natural_gradient."""
     from . import sr
     if group is not None:
         raise NotImplementedError("SPRING over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
     sr._check_damping(damping, relative_damping)
     sr._check_spring(momentum, 0.0, clip)
+    sr._check_solver(solver, tol, max_iter)
     model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
     inv = 1.0 / (ps + 1e-8)
     e_loc = hpsi * inv
     rows = model.psi_jacobian(x, w_psi=inv)
-    d = sr.spring_direction(rows, e_loc, prev.to(rows.device), momentum, damping=damping, relative_damping=relative_damping, clip=clip)
+    d = sr.spring_direction(rows, e_loc, prev.to(rows.device), momentum, damping=damping, relative_damping=relative_damping, clip=clip,
+                            **_solver_args(solver, tol, max_iter))
     return d, float(e_loc.double().mean())
 
 
@@ -312,7 +322,8 @@ def spring_step_size(learning_rate, d, norm_constraint):
 
 def train_step_spring(epoch, psi, h_fn, params, batch, learning_rate, prev, momentum, norm_constraint, clip, group=None, **damping):
     """One SPRING step theta <- theta - eff d with d = spring_direction(...) and eff = spring_step_size(lr, d, norm_constraint)
-    -> (new params, d, loss); the caller passes d as `prev` of the next step.  `params` is left as it is, as in train_step_sr."""
+    -> (new params, d, loss); the caller passes d as `prev` of the next step.  `params` is left as it is, as in train_step_sr.  `damping` also
+    carries solver / tol / max_iter to spring_direction."""
     from . import sr
     sr._check_spring(momentum, norm_constraint, clip)
     d, loss_val = spring_direction(params, psi, h_fn, batch, prev, momentum, clip=clip, group=group, **damping)
@@ -485,6 +496,7 @@ class ModelTrainer:
         self.optimizer = 'adam'      # 'sr': stochastic reconfiguration steps (train_step_sr; eager unless sr_on_device), one process
         self.sr_damping = {}         # damping / relative_damping of train_step_sr (its defaults when empty)
         self.sr_on_device = False    # optimizer='sr' / 'spring': True runs the whole step on the device (wf_vqmc_sr_step / wf_vqmc_spring_step), captured once when use_graph
+        self.sr_solver = 'cholesky'  # eager 'sr' / 'spring' steps: 'cg' solves matrix-free (sr.solve_cg), for batch_size beyond sr.MAX_WALKERS; the device-side steps are dense
         # optimizer='spring': train_step_spring (sr_on_device as for 'sr'; an empty sr_damping means SPRING_DEFAULTS['relative_damping']); DESIGN 4.21
         self.spring_momentum = SPRING_DEFAULTS["momentum"]
         self.spring_norm_constraint = SPRING_DEFAULTS["norm_constraint"]   # the step is capped at sqrt(this) in norm; 0: no cap
@@ -498,6 +510,8 @@ class ModelTrainer:
         optimizer = getattr(self, "optimizer", "adam")
         if optimizer not in ('adam', 'sr', 'spring'):
             raise ValueError(f"optimizer must be 'adam', 'sr' or 'spring', got {optimizer!r}")
+        if optimizer in ('sr', 'spring'):
+            self._sr_solver_args()
         distributed = dist.is_available() and dist.is_initialized()
         if optimizer in ('sr', 'spring') and (distributed or group is not None):
             raise NotImplementedError(f"optimizer={optimizer!r} runs in one process: stochastic reconfiguration over sharded walkers is not implemented")
@@ -590,11 +604,24 @@ class ModelTrainer:
             return new_loss
         return self._train_host(run, step, save_optimizer=True)
 
+    def _sr_solver_args(self):
+        """{} for the dense solve, {"solver": 'cg'} for the matrix-free one; ValueError for a solver the steps do not know, and for 'cg' together
+        with sr_on_device (wf_vqmc_sr_step and wf_vqmc_spring_step factorise the B x B matrix)."""
+        from . import sr
+        solver = getattr(self, "sr_solver", "cholesky")
+        sr._check_solver(solver)
+        if solver == 'cholesky':
+            return {}
+        if getattr(self, "sr_on_device", False):
+            raise ValueError(f"sr_solver={solver!r} with sr_on_device=True: the device-side steps solve densely (at most {sr.MAX_WALKERS} walkers); "
+                             "use sr_on_device=False for the matrix-free solve")
+        return {"solver": solver}
+
     def _train_sr(self, run):
         """The host-stepped loop with train_step_sr in the place of the Adam step: eager (the solver's status is read every step), parameters on
         the device in opt_state.x, no optimiser state to save."""
         def step(epoch, params, batch):
-            new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}))
+            new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}), **self._sr_solver_args())
             run.opt_state.x.copy_(new_params.flat)
             run.opt_state.version += 1
             return new_loss
@@ -679,7 +706,7 @@ class ModelTrainer:
 
         def step(epoch, params, batch):
             new_params, d, new_loss = train_step_spring(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, phi, momentum, cap, clip,
-                                                        **self._spring_damping())
+                                                        **self._spring_damping(), **self._sr_solver_args())
             capped[0] += int(spring_step_size(_lr_at(self.learning_rate, epoch), d, cap) < float(np.float32(_lr_at(self.learning_rate, epoch))))
             phi.copy_(d)
             run.opt_state.x.copy_(new_params.flat)
