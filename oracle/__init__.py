@@ -214,11 +214,13 @@ class Model:
             m.psp_plain = b32.ctypes.data
             m.ob_to_b = o2b32.ctypes.data
             self.p_nb = ob32.shape[1]
+            self.p_tab = ob32
         elif prior == "mflow":
             tab = np.ascontiguousarray(table(KIND_M, p_k, p_knots, n_mesh), dtype=np.float32)
             self.keep.append(tab)
             self._spline(m.psp, p_k, tab, {0: 0} if p_left is None else p_left, {0: 0} if p_right is None else p_right, n_mesh)
             self.p_nb = tab.shape[1]
+            self.p_tab = tab
         m.n_constr_left = len(constr_left)
         for i, c in enumerate(constr_left):
             m.constr_left[i] = int(c)
@@ -344,13 +346,53 @@ class Model:
         assert rc == 0
         return dens, ymax.value
 
-    def flow_direct(self, params, x):
+    def prior_rosenblatt(self, params, lat, threads=1, ncol=None, return_density=False):
+        """Rosenblatt transform of latent points lat [B, D] under the law the samplers are to draw from (wfo_prior_rosenblatt, fp64 library):
+        v[b, d] = F_d(lat[b, d] | lat[b, <d]), the normalised cumulative of prior_column_density's density of column d, integrated in closed
+        form over the mesh intervals -- i.i.d. uniform on the unit cube exactly when the law is right -- and Z[b, d], the integral of that
+        density over [0, 1].  ncol: the first ncol columns only (column 0 alone costs one table for the whole batch).
+        return_density: also the unnormalised density at lat[b, d] and the rejection bound ymax[b, d]."""
+        assert self.c.prior_kind in (0, 1), "Normal / Uniform priors need no oracle: v = Phi(lat) / v = lat"
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.size == self.n_params(), (params.size, self.n_params())
+        lat = np.ascontiguousarray(lat, dtype=np.float32).reshape(-1, self.D)
+        B, ncol = lat.shape[0], self.D if ncol is None else int(ncol)
+        v, Z = np.zeros((B, ncol)), np.zeros((B, ncol))
+        dens, ymax = (np.zeros((B, ncol)), np.zeros((B, ncol))) if return_density else (None, None)
+        L = lib(True)
+        L.wfo_prior_rosenblatt.restype = ctypes.c_int
+        L.wfo_prior_rosenblatt.argtypes = [ctypes.POINTER(_Model), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + \
+                                          [ctypes.c_void_p] * 4 + [ctypes.c_int]
+        rc = L.wfo_prior_rosenblatt(ctypes.byref(self.c), params.ctypes.data, lat.ctypes.data, B, ncol, v.ctypes.data, Z.ctypes.data,
+                                    dens.ctypes.data if return_density else None, ymax.ctypes.data if return_density else None, int(threads))
+        if rc:
+            raise RuntimeError(f"wfo_prior_rosenblatt rc={rc}")
+        return (v, Z, dens, ymax) if return_density else (v, Z)
+
+    def prior_column_coeffs(self, params, lat, col, threads=1):
+        """-> (coef [B, nb], ymax [B]), fp64: the spline coefficients (on the prior's table) of column `col`'s density given lat[b, <col], and the
+        rejection sampler's bound (wfo_prior_column_coeffs)."""
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        lat = np.ascontiguousarray(lat, dtype=np.float32).reshape(-1, self.D)
+        B = lat.shape[0]
+        coef, ymax = np.zeros((B, self.p_nb)), np.zeros(B)
+        L = lib(True)
+        L.wfo_prior_column_coeffs.restype = ctypes.c_int
+        L.wfo_prior_column_coeffs.argtypes = [ctypes.POINTER(_Model), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        rc = L.wfo_prior_column_coeffs(ctypes.byref(self.c), params.ctypes.data, lat.ctypes.data, B, int(col), coef.ctypes.data,
+                                       ymax.ctypes.data, int(threads))
+        if rc:
+            raise RuntimeError(f"wfo_prior_column_coeffs rc={rc}")
+        return coef, ymax
+
+    def flow_direct(self, params, x, f64=False):
         params = np.ascontiguousarray(params, dtype=np.float32)
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.D)
         u = np.zeros_like(x)
         ld = np.zeros(x.shape[0], np.float32)
-        lib().wfo_flow_direct(ctypes.byref(self.c), params.ctypes.data, x.ctypes.data, x.shape[0], u.ctypes.data,
-                              ld.ctypes.data)
+        lib(f64).wfo_flow_direct(ctypes.byref(self.c), params.ctypes.data, x.ctypes.data, x.shape[0], u.ctypes.data,
+                                 ld.ctypes.data)
         return u, ld
 
 

@@ -726,22 +726,25 @@ int wfo_inverse(const wfo_model* m, const float* params, const float* u, int64_t
     return 0;
 }
 
-/* The density the reference's rejection sampler draws column `col` from, given the already drawn columns
- * (wavefunctions.py:89-104 / distributions.py:170-186): value at x, and the sampler's upper bound ymax.
- * outputs: [D] with zeros in the columns not drawn yet. */
-int wfo_prior_column_density(const wfo_model* m, const float* params, const float* outputs, int col, const float* xs, int n,
-                             float* dens, float* ymax_out) {
-    int D = m->D, nb = m->psp.nb, H = m->hidden;
+/* Parameters of the prior's conditioner: behind the flow layers' nets. */
+static const float* prior_params(const wfo_model* m, const float* params) {
+    int D = m->D, H = m->hidden;
     int n_out_l = m->layer_kind == 0 ? m->isp.nb : 2;
     int64_t per_layer = (int64_t)D * H + H + (int64_t)H * H + H + (int64_t)H * n_out_l * D + (int64_t)n_out_l * D + (m->layer_kind == 0 ? (int64_t)D * n_out_l : 0);
-    const float* pp = params + per_layer * m->n_layers;
-    real o[WFO_MAX_D], bij[WFO_MAX_D * WFO_MAX_NB];
-    for (int d = 0; d < D; ++d) o[d] = (real)outputs[d];
+    return params + per_layer * m->n_layers;
+}
+
+/* Coefficients of the spline whose value (M prior) or square (B prior) is the density of column `col` given the columns drawn so far
+ * (o: [D], zeros in the columns not drawn yet), on the prior table m->psp.tab, and the rejection sampler's bound ymax
+ * (wavefunctions.py:89-104 + bsplines_jax.py:144-171 / distributions.py:170-186 + msplines_jax.py:147-150). */
+static int prior_column_coeffs(const wfo_model* m, const float* pp, const real* o, int col, real* c /* [nb] */, real* ymax_out) {
+    int D = m->D, nb = m->psp.nb, H = m->hidden;
+    real bij[WFO_MAX_D * WFO_MAX_NB];
     if (m->prior_kind == 0) {
         bijection_params(pp, D, H, nb, 1, m->p_gate, o, bij);
         real* w = bij + col * nb;
         enforce_bc(&m->psp, m->psp_plain, 2, w);
-        real c[WFO_MAX_NB], ss = C(0.0);
+        real ss = C(0.0);
         for (int j = 0; j < nb; ++j) {
             real acc = C(0.0);
             for (int a = 0; a < nb; ++a) acc = acc + w[a] * m->ob_to_b[a * nb + j];
@@ -755,8 +758,7 @@ int wfo_prior_column_density(const wfo_model* m, const float* params, const floa
             for (int a = 0; a < nb; ++a) acc = acc + c[a] * m->b_to_ob[a * nb + j];
             if (acc * acc > ymax) ymax = acc * acc;
         }
-        *ymax_out = (float)ymax;
-        for (int i = 0; i < n; ++i) { real v = spline_apply(&m->psp, 0, c, (real)xs[i], 0); dens[i] = (float)(v * v); }
+        *ymax_out = ymax;
     } else if (m->prior_kind == 1) {
         bijection_params(pp, D, H, nb, 0, m->p_gate, o, bij);
         real* w = bij + col * nb;
@@ -764,10 +766,136 @@ int wfo_prior_column_density(const wfo_model* m, const float* params, const floa
         enforce_bc(&m->psp, m->psp.tab, 0, w);
         real mx = w[0];
         for (int j = 1; j < nb; ++j) if (w[j] > mx) mx = w[j];
-        *ymax_out = (float)(mx * (real)(nb + m->psp.k));   /* params.max() * n_knots, msplines_jax.py:147-150 */
-        for (int i = 0; i < n; ++i) dens[i] = (float)spline_apply(&m->psp, 0, w, (real)xs[i], 0);
+        *ymax_out = mx * (real)(nb + m->psp.k);   /* params.max() * n_knots, msplines_jax.py:147-150 */
+        for (int j = 0; j < nb; ++j) c[j] = w[j];
     } else return -1;
     return 0;
+}
+
+/* The density the reference's rejection sampler draws column `col` from, given the already drawn columns
+ * (wavefunctions.py:89-104 / distributions.py:170-186): value at x, and the sampler's upper bound ymax.
+ * outputs: [D] with zeros in the columns not drawn yet. */
+int wfo_prior_column_density(const wfo_model* m, const float* params, const float* outputs, int col, const float* xs, int n,
+                             float* dens, float* ymax_out) {
+    int D = m->D;
+    const float* pp = prior_params(m, params);
+    real o[WFO_MAX_D], c[WFO_MAX_NB], ymax;
+    for (int d = 0; d < D; ++d) o[d] = (real)outputs[d];
+    if (prior_column_coeffs(m, pp, o, col, c, &ymax)) return -1;
+    *ymax_out = (float)ymax;
+    for (int i = 0; i < n; ++i) {
+        real v = spline_apply(&m->psp, 0, c, (real)xs[i], 0);
+        dens[i] = (float)(m->prior_kind == 0 ? v * v : v);
+    }
+    return 0;
+}
+
+/* Rosenblatt transform of latent points under the law the samplers are to draw from: column d of a walker follows the density of
+ * wfo_prior_column_density given the walker's columns < d (zeros elsewhere), so v[b][d] = F_d(lat[b][d] | lat[b][<d]) -- F_d the
+ * normalised cumulative of that density over [0, 1] -- is uniform on the unit cube, independent across columns and walkers, exactly
+ * when the law is right.  spline_apply interpolates the table linearly between mesh points, so the density is a quadratic (B prior:
+ * the square of a linear piece) or linear (M prior) polynomial on each mesh interval and is integrated in closed form: no quadrature
+ * error.  Accumulation in double in either build; use the fp64 library, whose coefficients are double too.
+ *   lat [B][D] -> v [B][ncol], Z [B][ncol] = the integral of the density over [0, 1], dens [B][ncol] = the (unnormalised) density at
+ *   lat[b][d], ymax [B][ncol] = the rejection bound (each optional).  Columns 0 .. ncol-1 only (column 0 does not depend on the
+ *   walker: its cumulative table is built once). */
+static void mesh_cumulative(const wfo_model* m, const real* c, double* f, double* cum) {
+    const wfo_spline* s = &m->psp;
+    int n = s->n_mesh;
+    double h = 1.0 / (double)(n - 1);
+    for (int q = 0; q < n; ++q) f[q] = 0.0;
+    for (int j = 0; j < s->nb; ++j) {
+        const float* row = s->tab + (size_t)j * n;      /* derivative order 0 */
+        double cj = (double)c[j];
+        for (int q = 0; q < n; ++q) f[q] += cj * (double)row[q];
+    }
+    cum[0] = 0.0;
+    for (int q = 0; q + 1 < n; ++q) {
+        double a = f[q], b = f[q + 1];
+        cum[q + 1] = cum[q] + (m->prior_kind == 0 ? h * (a * a + a * b + b * b) / 3.0 : h * (a + b) / 2.0);
+    }
+}
+
+static void rosenblatt_at(const wfo_model* m, const double* f, const double* cum, double x, double* v, double* Z, double* dens) {
+    int n = m->psp.n_mesh;
+    double h = 1.0 / (double)(n - 1);
+    double xs = x * (double)(n - 1);
+    int q = (int)floor(xs);
+    if (q < 0) q = 0;
+    if (q > n - 2) q = n - 2;
+    double t = xs - (double)q, a = f[q], e = f[q + 1] - f[q];
+    double fx = a + e * t;
+    double part = m->prior_kind == 0 ? h * (a * a * t + a * e * t * t + e * e * t * t * t / 3.0) : h * (a * t + e * t * t / 2.0);
+    if (v) *v = (cum[q] + part) / cum[n - 1];
+    if (Z) *Z = cum[n - 1];
+    if (dens) *dens = m->prior_kind == 0 ? fx * fx : fx;
+}
+
+/* prior_column_coeffs of column `col` for B walkers (lat [B][D]: the columns < col condition, the others are ignored): coef [B][nb],
+ * ymax [B].  For a host restatement of the rejection sampler (tests/sampler_law.py). */
+int wfo_prior_column_coeffs(const wfo_model* m, const float* params, const float* lat, int64_t B, int col, double* coef, double* ymax,
+                            int threads) {
+    int D = m->D, nb = m->psp.nb;
+    if ((m->prior_kind != 0 && m->prior_kind != 1) || D > WFO_MAX_D || nb > WFO_MAX_NB || col < 0 || col >= D) return -1;
+    const float* pp = prior_params(m, params);
+#pragma omp parallel for schedule(static) num_threads(threads > 1 ? threads : 1)
+    for (int64_t b = 0; b < B; ++b) {
+        real o[WFO_MAX_D], c[WFO_MAX_NB], ym;
+        for (int e = 0; e < D; ++e) o[e] = e < col ? (real)lat[b * D + e] : C(0.0);
+        prior_column_coeffs(m, pp, o, col, c, &ym);
+        for (int j = 0; j < nb; ++j) coef[b * nb + j] = (double)c[j];
+        ymax[b] = (double)ym;
+    }
+    return 0;
+}
+
+/* The Rosenblatt transform itself (described above mesh_cumulative). */
+int wfo_prior_rosenblatt(const wfo_model* m, const float* params, const float* lat, int64_t B, int ncol, double* v, double* Z,
+                         double* dens, double* ymax, int threads) {
+    int D = m->D, n = m->psp.n_mesh;
+    if (m->prior_kind != 0 && m->prior_kind != 1) return -1;
+    if (D > WFO_MAX_D || m->psp.nb > WFO_MAX_NB || ncol < 1 || ncol > D || n < 2) return -1;
+    const float* pp = prior_params(m, params);
+    double* f0 = (double*)malloc(sizeof(double) * 2 * (size_t)n);
+    if (!f0) return -3;
+    double ymax0;
+    {
+        real o[WFO_MAX_D], c[WFO_MAX_NB], ym;
+        for (int d = 0; d < D; ++d) o[d] = C(0.0);
+        prior_column_coeffs(m, pp, o, 0, c, &ym);
+        mesh_cumulative(m, c, f0, f0 + n);
+        ymax0 = (double)ym;
+    }
+    int failed = 0;
+#pragma omp parallel num_threads(threads > 1 ? threads : 1)
+    {
+        double* f = ncol > 1 ? (double*)malloc(sizeof(double) * 2 * (size_t)n) : 0;
+        if (ncol > 1 && !f) {
+#pragma omp atomic write
+            failed = 1;
+        }
+#pragma omp for schedule(static)
+        for (int64_t b = 0; b < B; ++b) {
+            if (ncol > 1 && !f) continue;
+            for (int d = 0; d < ncol; ++d) {
+                size_t at = (size_t)b * ncol + d;
+                double x = (double)lat[b * D + d], ym = ymax0;
+                const double *ff = f0, *cc = f0 + n;
+                if (d > 0) {
+                    real o[WFO_MAX_D], c[WFO_MAX_NB], ymr;
+                    for (int e = 0; e < D; ++e) o[e] = e < d ? (real)lat[b * D + e] : C(0.0);
+                    prior_column_coeffs(m, pp, o, d, c, &ymr);
+                    mesh_cumulative(m, c, f, f + n);
+                    ff = f; cc = f + n; ym = (double)ymr;
+                }
+                rosenblatt_at(m, ff, cc, x, v ? v + at : 0, Z ? Z + at : 0, dens ? dens + at : 0);
+                if (ymax) ymax[at] = ym;
+            }
+        }
+        free(f);
+    }
+    free(f0);
+    return failed ? -3 : 0;
 }
 
 /* ------------------------------------------------------------------ */

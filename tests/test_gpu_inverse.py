@@ -68,12 +68,11 @@ def test_sampler_draws_from_the_prior_columns_and_is_reproducible(he_flat):
     cdf /= cdf[-1]
     emp = np.searchsorted(np.sort(lat[:, 0]), grid) / n
     assert np.abs(emp - cdf).max() < 4.0 / np.sqrt(n)       # Kolmogorov-Smirnov, ~1e-6 false-alarm level
-    # column 1 given column 0 in a narrow bin
-    sel = np.abs(lat[:, 0] - 0.7) < 0.004
-    dens1, _ = om.prior_column_density(he_flat, [0.7, 0], 1, grid)
-    cdf1 = np.concatenate([[0], np.cumsum(0.5 * (dens1[1:] + dens1[:-1]) * np.diff(grid))]); cdf1 /= cdf1[-1]
-    emp1 = np.searchsorted(np.sort(lat[sel, 1]), grid) / sel.sum()
-    assert np.abs(emp1 - cdf1).max() < 4.0 / np.sqrt(sel.sum()) + 0.02
+    # column 1 given column 0, every walker at its own conditioning value: the oracle's fp64 Rosenblatt transform of the latent points is uniform on the
+    # unit square, columns and neighbouring walkers independent (tests/sampler_law.py: Kolmogorov-Smirnov and 8 x 8 chi-squares, each p > 1e-6)
+    import sampler_law
+    assert np.array_equal(sampler_law.flat_params("he"), he_flat)
+    sampler_law.assert_uniform(sampler_law.rosenblatt("he", lat)[0], "He, default path, 200 000 walkers")
     # exact inverse => x ~ |psi|^2: direct(x) gives back the latent, walkers are sorted and inside the box
     xn = x.cpu().numpy()
     assert np.all(xn[:, 0] <= xn[:, 1] + 1e-4) and np.abs(xn).max() <= 10.0 + 1e-3
