@@ -15,7 +15,7 @@ SOURCES = ["wf_tables.cpp", "wf_runtime.cpp", "wf_model_build.cpp", "wf_model_im
            "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip",
            "wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_sample.hip", "wf_kernels_etile_dir.hip", "wf_kernels_spline.hip",
            "wf_kernels_sr.hip", "wf_kernels_sr_step.hip", "wf_kernels_sr_spring.hip", "wf_kernels_sr_cg.hip", "wf_kernels_observe.hip", "wf_kernels_dmc.hip",
-           "wf_train_dmc_observe.cpp", "wf_kernels_dmc_observe.hip"]
+           "wf_train_dmc_observe.cpp", "wf_kernels_dmc_observe.hip", "wf_train_overlap.cpp", "wf_kernels_overlap.hip"]
 # -ffp-contract=off: the index arithmetic and the table lerp keep the reference's separate
 # multiply / add roundings; dot products that may fuse say so with explicit fmaf / MFMA.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
@@ -82,7 +82,7 @@ def _library_current():
         return False
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
     deps += [os.path.join(HERE, "..", "include", h) for h in ("waveflow_hip.h", "waveflow_sr.h", "waveflow_sr_step.h", "waveflow_sr_spring.h", "waveflow_sr_cg.h", "waveflow_observe.h", "waveflow_dmc.h",
-                                                                "waveflow_dmc_observe.h")]
+                                                                "waveflow_dmc_observe.h", "waveflow_overlap.h")]
     return all(os.path.getmtime(d) <= t for d in deps if os.path.exists(d))
 
 

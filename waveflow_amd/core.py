@@ -563,6 +563,40 @@ class DeviceModel:
                                                           self._p(x), int(walkers is None), self._p(values), *ws, self._stream()),
                    "wf_vqmc_observe_step")
 
+    # ---- one overlap measurement step on the device (include/waveflow_overlap.h; overlap.measure drives it)
+    def overlap_step_workspace_bytes(self, batch, K):
+        """Workspace of overlap_step for `batch` walkers per step and K reference models; WfError where the library has no such step."""
+        from . import overlap
+        return _lib.check(overlap.lib().wf_vqmc_overlap_step_workspace_bytes(self._h, int(batch), int(K)), "wf_vqmc_overlap_step_workspace_bytes")
+
+    def overlap_step(self, refs, acc, counter, seed, batch, exact_sampler=True, walkers=None, out_walkers=None, ratios=None):
+        """One overlap measurement step on the device (wf_vqmc_overlap_step): no host work, no wait, capturable in a hipGraph after one call
+        outside the capture.  The step draws its walkers from this model (stream `seed` advanced by `counter`, one int64 on the device, + 1 at
+        the end; out_walkers [batch, D], if given, receives them) or reads them from `walkers` [batch, D]; it evaluates psi of this model and of
+        every DeviceModel of `refs` (1 .. 8 of them, on this device, with this D, holding their parameters; this model may be among them) on
+        them, adds r_k = psi_k / (psi + 1e-8) to `acc` (an overlap.Accumulator; None with `ratios`) and writes them to `ratios` [K, batch] if
+        given.  No model changes.  Arguments are checked before anything is launched (ValueError)."""
+        from . import overlap
+        refs = list(refs)
+        K = overlap._check_K(len(refs))
+        batch = overlap._check_step(batch, self.D, K, walkers, out_walkers, ratios)
+        for r in refs:
+            if not isinstance(r, DeviceModel) or r.D != self.D or r.device != self.device:
+                raise ValueError(f"every reference must be a DeviceModel of {self.D} coordinates on device {self.device}")
+        if acc is None and ratios is None:
+            raise ValueError("nothing to do: neither an accumulator nor ratios")
+        if acc is not None and (not isinstance(acc, overlap.Accumulator) or acc.K != K):
+            raise ValueError(f"the accumulator must be an overlap.Accumulator of {K} reference states")
+        if not hasattr(counter, "is_cuda") or counter.numel() != 1 or str(counter.dtype) != "torch.int64" or not counter.is_cuda:
+            raise ValueError("counter must be one int64 on the device (no CPU fallback)")
+        st = acc.st if acc is not None else {"x": counter, "ws": None}
+        ws = self._train_ws(st, self.overlap_step_workspace_bytes(batch, K))
+        handles = (ctypes.c_void_p * K)(*[r._h.value for r in refs])
+        x = walkers if walkers is not None else out_walkers
+        _lib.check(overlap.lib().wf_vqmc_overlap_step(self._h, handles, K, ctypes.byref(acc.c) if acc is not None else None, self._p(counter),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, batch, int(bool(exact_sampler)), self._p(x), int(walkers is None),
+                                                      self._p(ratios), *ws, self._stream()), "wf_vqmc_overlap_step")
+
     # ---- fixed-node diffusion Monte Carlo on the device (include/waveflow_dmc.h; dmc.run drives it)
     def dmc_workspace_bytes(self, n_walkers):
         """Workspace of dmc_init and dmc_step for a population of n_walkers; WfError where the library has no such step for this model or size."""

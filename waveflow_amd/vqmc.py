@@ -80,13 +80,18 @@ def adam(step_size, b1=0.9, b2=0.999, eps=1e-8, model=None):
     return opt_init, opt_update, get_params
 
 
+def _model_init_fun(box_length, n_particle, xu_coord_type, spline_degree, num_knots, n_flow_layers):
+    """The model of create_train_state: init_fun(rng, n_particle) -> (params, psi, log_pdf, sample) on a DeviceModel of its own."""
+    return get_waveflow_model(n_particle, base_spline_degree=spline_degree, i_spline_degree=spline_degree,
+                              n_prior_internal_knots=num_knots, n_i_internal_knots=num_knots,
+                              i_spline_reg=0.05, i_spline_reverse_fun_tol=0.000001,
+                              n_flow_layers=n_flow_layers, box_size=box_length, xu_coord_type=xu_coord_type)
+
+
 def create_train_state(box_length, learning_rate, n_particle, rng=0, xu_coord_type='mean', spline_degree=6, num_knots=23,
                        n_flow_layers=3):
     """vqmc.py:123-139"""
-    init_fun = get_waveflow_model(n_particle, base_spline_degree=spline_degree, i_spline_degree=spline_degree,
-                                  n_prior_internal_knots=num_knots, n_i_internal_knots=num_knots,
-                                  i_spline_reg=0.05, i_spline_reverse_fun_tol=0.000001,
-                                  n_flow_layers=n_flow_layers, box_size=box_length, xu_coord_type=xu_coord_type)
+    init_fun = _model_init_fun(box_length, n_particle, xu_coord_type, spline_degree, num_knots, n_flow_layers)
     params, psi, log_pdf, sample = init_fun(rng, n_particle)
     opt_init, opt_update, get_params = adam(step_size=learning_rate, model=psi.model)   # state on the model's GPU
     return psi, log_pdf, sample, opt_init(params), opt_update, get_params
@@ -254,13 +259,61 @@ def log_psi_jacobian(psi):
     return jac
 
 
-def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=1e-3, group=None, solver='cholesky', tol=1e-8, max_iter=2000):
+def _check_lower_states(lower_states, overlap_penalty):
+    """lower_states: a list of (psi closure, params), at most overlap.MAX_REFS; overlap_penalty: one number or one per state, >= 0
+    -> (the list, float32 [K]); ([], None) for None or an empty list.  Before anything is launched (ValueError)."""
+    if not lower_states:
+        return [], None
+    from . import overlap
+    lower_states = list(lower_states)
+    overlap._check_K(len(lower_states))
+    for entry in lower_states:
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2 or getattr(entry[0], "model", None) is None:
+            raise ValueError("lower_states must be a list of (psi closure of model_factory's init_fun, params)")
+    return lower_states, overlap._check_penalty(overlap_penalty, len(lower_states))
+
+
+def _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_record):
+    """The local energies of the penalty method L = E + sum_k lambda_k S_k^2 on the walkers x of `model` (psi `ps` and local energies
+    `e_loc` on them): every lower psi at x through its own model's psi (its parameters are uploaded when they are not the ones it holds:
+    once), overlap.accumulate into a fresh accumulator, overlap.penalise -> e~ float32 cuda [B].  overlap_record, a list, receives S_k of
+    the step (float64 numpy [K]; this waits for the device)."""
+    import torch
+    from . import overlap
+    rows = []
+    for lpsi, lparams in lower_states:
+        lm = lpsi.model
+        if lm is model:
+            raise ValueError("a lower state must have a DeviceModel of its own: it shares the model being trained")
+        if lm.D != model.D or lm.device != model.device:
+            raise ValueError(f"a lower state has {lm.D} coordinates on device {lm.device}, the model {model.D} on device {model.device}")
+        lm.ensure_params(lparams)
+        rows.append(lm.psi(x))
+    refs = torch.stack(rows)
+    acc = overlap.Accumulator(len(rows), x.device)
+    ratios = overlap.accumulate(ps, refs, acc=acc, ratios=torch.empty_like(refs))
+    e_pen = overlap.penalise(e_loc, ratios, acc, penalty)
+    if overlap_record is not None:
+        overlap_record.append(acc.totals().result()["overlap"])
+    return e_pen
+
+
+def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=1e-3, group=None, solver='cholesky', tol=1e-8, max_iter=2000, *,
+                        lower_states=None, overlap_penalty=0.0, overlap_record=None):
     """Stochastic reconfiguration on the walkers of `batch`: d = (S + lambda I)^-1 g with O_k(x_b) = d ln psi_b / d theta_k (the rows of
     log_psi_jacobian, written once with the weight 1 / (psi + 1e-8)), S = O^T H O / B, g = (2 / B) O^T H e_loc, e_loc = H psi / (psi + 1e-8)
     and lambda = damping + relative_damping * trace(H O O^T H / B) / B, solved in its B x B form (waveflow_amd.sr).
     -> (d float32 cuda [n_params], loss = mean e_loc).  Sharded walkers (`group`) are not supported.  solver='cg' (with tol, max_iter): the
-    matrix-free solve of sr.solve_cg, for batches beyond sr.MAX_WALKERS."""
+    matrix-free solve of sr.solve_cg, for batches beyond sr.MAX_WALKERS.
+
+    Excited states.  lower_states: a list of (psi closure, params) of states to stay orthogonal to, each closure on a DeviceModel of its own
+    (another init_fun call); overlap_penalty: lambda, one number or one per state, >= 0.  The solver then receives the local energies of
+    L = E + sum_k lambda_k S_k^2 (overlap.penalise: e~_b = e_b + sum_k lambda_k a_k (r_kb - a_k) with r_k = psi_k / (psi + 1e-8) and a_k its
+    batch mean) in the place of e_loc; the returned loss stays the mean of the unpenalised e_loc.  overlap_record: a list that receives S_k of
+    this step's walkers (float64 numpy [K]) -- how every function of this module that takes lower_states reports the overlaps; the return
+    values keep their shape.  With lower_states None or empty nothing of this is called and the result is bit for bit the one without."""
     from . import sr
+    lower_states, penalty = _check_lower_states(lower_states, overlap_penalty)
     if group is not None:
         raise NotImplementedError("stochastic reconfiguration over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
     sr._check_damping(damping, relative_damping)
@@ -269,7 +322,8 @@ def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=
     inv = 1.0 / (ps + 1e-8)
     e_loc = hpsi * inv
     rows = model.psi_jacobian(x, w_psi=inv)
-    d = sr.natural_gradient(rows, e_loc, damping=damping, relative_damping=relative_damping, **_solver_args(solver, tol, max_iter))
+    e_used = _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_record) if lower_states else e_loc
+    d = sr.natural_gradient(rows, e_used, damping=damping, relative_damping=relative_damping, **_solver_args(solver, tol, max_iter))
     return d, float(e_loc.double().mean())
 
 
@@ -278,11 +332,17 @@ def _solver_args(solver, tol, max_iter):
     return {} if solver == 'cholesky' else {"solver": solver, "tol": tol, "max_iter": max_iter}
 
 
-def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **damping):
+def _overlap_args(lower_states, overlap_penalty, overlap_record):
+    """The excited-state keywords for sr_natural_gradient / spring_direction: none without lower states, whose call stays as it was."""
+    return {"lower_states": lower_states, "overlap_penalty": overlap_penalty, "overlap_record": overlap_record} if lower_states else {}
+
+
+def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, *, lower_states=None, overlap_penalty=0.0, overlap_record=None, **damping):
     """One stochastic-reconfiguration step theta <- theta - lr d (sr_natural_gradient; `damping`: its damping / relative_damping, and solver / tol / max_iter;
     learning_rate: a number, or a schedule called with `epoch`) -> (new params, loss).  `params` is left as it is: the result is a new
-    pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one."""
-    d, loss_val = sr_natural_gradient(params, psi, h_fn, batch, group=group, **damping)
+    pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one.  lower_states, overlap_penalty, overlap_record:
+    as in sr_natural_gradient."""
+    d, loss_val = sr_natural_gradient(params, psi, h_fn, batch, group=group, **damping, **_overlap_args(lower_states, overlap_penalty, overlap_record))
     lr = _lr_at(learning_rate, epoch)
     if isinstance(params, DeviceParams):
         return DeviceParams(params.template, params.flat - lr * d.to(params.flat.device), params.version + 1), loss_val
@@ -291,12 +351,14 @@ def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, **
 
 
 def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0, group=None, solver='cholesky', tol=1e-8,
-                     max_iter=2000):
+                     max_iter=2000, *, lower_states=None, overlap_penalty=0.0, overlap_record=None):
     """The SPRING direction on the walkers of `batch` (sr.spring_direction on the rows and local energies of sr_natural_gradient): stochastic
     reconfiguration pulled towards momentum * prev, local energies clamped `clip` mean absolute deviations around their median (0: not clamped).
     prev: the previous direction, float32 cuda [n_params] (zeros at the start).  -> (d float32 cuda [n_params], loss = mean of the unclipped e_loc).
-    Sharded walkers (`group`) are not supported.  solver, tol, max_iter: as in sr_natural_gradient."""
+    Sharded walkers (`group`) are not supported.  solver, tol, max_iter: as in sr_natural_gradient.  lower_states, overlap_penalty,
+    overlap_record: as in sr_natural_gradient -- the clip then clamps the penalised energies around their median."""
     from . import sr
+    lower_states, penalty = _check_lower_states(lower_states, overlap_penalty)
     if group is not None:
         raise NotImplementedError("SPRING over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
     sr._check_damping(damping, relative_damping)
@@ -306,7 +368,8 @@ def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, rela
     inv = 1.0 / (ps + 1e-8)
     e_loc = hpsi * inv
     rows = model.psi_jacobian(x, w_psi=inv)
-    d = sr.spring_direction(rows, e_loc, prev.to(rows.device), momentum, damping=damping, relative_damping=relative_damping, clip=clip,
+    e_used = _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_record) if lower_states else e_loc
+    d = sr.spring_direction(rows, e_used, prev.to(rows.device), momentum, damping=damping, relative_damping=relative_damping, clip=clip,
                             **_solver_args(solver, tol, max_iter))
     return d, float(e_loc.double().mean())
 
@@ -320,13 +383,15 @@ def spring_step_size(learning_rate, d, norm_constraint):
     return float(np.float32(eff))
 
 
-def train_step_spring(epoch, psi, h_fn, params, batch, learning_rate, prev, momentum, norm_constraint, clip, group=None, **damping):
+def train_step_spring(epoch, psi, h_fn, params, batch, learning_rate, prev, momentum, norm_constraint, clip, group=None, *, lower_states=None,
+                      overlap_penalty=0.0, overlap_record=None, **damping):
     """One SPRING step theta <- theta - eff d with d = spring_direction(...) and eff = spring_step_size(lr, d, norm_constraint)
     -> (new params, d, loss); the caller passes d as `prev` of the next step.  `params` is left as it is, as in train_step_sr.  `damping` also
-    carries solver / tol / max_iter to spring_direction."""
+    carries solver / tol / max_iter to spring_direction.  lower_states, overlap_penalty, overlap_record: as in sr_natural_gradient."""
     from . import sr
     sr._check_spring(momentum, norm_constraint, clip)
-    d, loss_val = spring_direction(params, psi, h_fn, batch, prev, momentum, clip=clip, group=group, **damping)
+    d, loss_val = spring_direction(params, psi, h_fn, batch, prev, momentum, clip=clip, group=group, **damping,
+                                   **_overlap_args(lower_states, overlap_penalty, overlap_record))
     eff = spring_step_size(_lr_at(learning_rate, epoch), d, norm_constraint)
     if isinstance(params, DeviceParams):
         return DeviceParams(params.template, params.flat - eff * d.to(params.flat.device), params.version + 1), d, loss_val
@@ -470,6 +535,16 @@ class _Run(SimpleNamespace):
 SPRING_DEFAULTS = {"momentum": 0.9, "norm_constraint": 0.1, "clip": 5.0, "relative_damping": 1e-2}
 
 
+def _check_distinct_start(flat0, lower_flat, k):
+    """An excited model must not start on the state it avoids: at psi = psi_k the ratio r is 1 on every walker, the penalty gradient
+    2 lambda a (r - a) vanishes and the point is a saddle the optimiser only leaves by noise.  ValueError when the initial parameters equal
+    lower state k bit for bit."""
+    a, b = np.ascontiguousarray(flat0, dtype=np.float32).reshape(-1), np.ascontiguousarray(lower_flat, dtype=np.float32).reshape(-1)
+    if a.size == b.size and np.array_equal(a.view(np.int32), b.view(np.int32)):
+        raise ValueError(f"lower_states[{k}] equals this trainer's initial parameters bit for bit: the overlap penalty has no gradient there; "
+                         "start the excited state from another seed")
+
+
 class ModelTrainer:
     """vqmc.py:19-119, same constructor arguments, attributes and on-disk artefacts."""
 
@@ -501,6 +576,51 @@ class ModelTrainer:
         self.spring_momentum = SPRING_DEFAULTS["momentum"]
         self.spring_norm_constraint = SPRING_DEFAULTS["norm_constraint"]   # the step is capped at sqrt(this) in norm; 0: no cap
         self.spring_clip = SPRING_DEFAULTS["clip"]                         # local energies clamped this many mean absolute deviations around the median; 0: off
+        # excited states (eager 'sr' / 'spring' loops): the states to stay orthogonal to -- result directories of earlier runs (their
+        # `checkpoints` file) or flat parameter vectors, loaded into models built with this trainer's settings -- and the penalty lambda of
+        # L = E + sum_k lambda_k S_k^2, one number or one per state (above the gap to the state avoided).  S_k per epoch: self.overlap_history
+        self.lower_states = []
+        self.overlap_penalty = 0.0
+
+    def _check_lower_state_settings(self, optimizer):
+        """What a non-empty lower_states excludes, before anything is built -> the penalties (float32 [K]), or None without lower states."""
+        lower = getattr(self, "lower_states", None)
+        if lower is None or len(lower) == 0:
+            return None
+        from . import overlap
+        if optimizer == 'adam':
+            raise ValueError("lower_states with optimizer='adam': the overlap penalty is built into the eager 'sr' and 'spring' steps only")
+        if getattr(self, "sr_on_device", False):
+            raise ValueError("lower_states with sr_on_device=True: the device-side steps have no overlap penalty; use sr_on_device=False")
+        try:
+            overlap._check_K(len(lower))
+        except ValueError as e:
+            raise ValueError(f"lower_states: {e}") from None
+        return overlap._check_penalty(getattr(self, "overlap_penalty", 0.0), len(lower))
+
+    def _load_lower_states(self, template, flat0):
+        """-> [(psi closure, DeviceParams)], one model per entry of lower_states, built with this trainer's model settings; its parameters from
+        the entry: a result directory (or its `checkpoints` file), or a flat vector.  ValueError for an entry of another size, and for one that
+        equals the initial parameters flat0 bit for bit (_check_distinct_start)."""
+        import torch
+        out = []
+        for k, entry in enumerate(self.lower_states):
+            if isinstance(entry, (str, os.PathLike)):
+                path = os.fspath(entry)
+                tree, _ = checkpoint.load_reference_checkpoint(os.path.join(path, "checkpoints") if os.path.isdir(path) else path)
+                flat = flatten_params(tree)
+            else:
+                flat = flatten_params(entry) if isinstance(entry, (DeviceParams, tuple, list)) else np.asarray(
+                    entry.detach().cpu().numpy() if hasattr(entry, "detach") else entry, dtype=np.float32).reshape(-1)
+            flat = np.ascontiguousarray(flat, dtype=np.float32)
+            if flat.size != flat0.size:
+                raise ValueError(f"lower_states[{k}] holds {flat.size} parameters, this trainer's model has {flat0.size}")
+            _check_distinct_start(flat0, flat, k)
+            init_fun = _model_init_fun(self.box_length, self.n_particle, self.xu_coord_type, self.spline_degree, self.num_knots, self.n_flow_layer)
+            _, psi_k, _, _ = init_fun(0, self.n_particle)
+            dev = torch.as_tensor(flat).to(f"cuda:{psi_k.model.device}")
+            out.append((psi_k, DeviceParams(template, dev)))
+        return out
 
     def start_training(self, restart=False, verbose=True, group=None):
         """Under torch.distributed (one process per GPU, `torchrun examples/run_vqmc.py`) the walkers of a step are split over
@@ -512,6 +632,7 @@ class ModelTrainer:
             raise ValueError(f"optimizer must be 'adam', 'sr' or 'spring', got {optimizer!r}")
         if optimizer in ('sr', 'spring'):
             self._sr_solver_args()
+        penalties = self._check_lower_state_settings(optimizer)
         distributed = dist.is_available() and dist.is_initialized()
         if optimizer in ('sr', 'spring') and (distributed or group is not None):
             raise NotImplementedError(f"optimizer={optimizer!r} runs in one process: stochastic reconfiguration over sharded walkers is not implemented")
@@ -554,6 +675,12 @@ class ModelTrainer:
         run = _Run(psi=psi, sample=sample, h_fn=h_fn, opt_state=opt_state, opt_update=opt_update, get_params=get_params, start_epoch=start_epoch,
                    loss=loss, energies=energies, system_dict=system_dict, save_dir=save_dir, rng=rng, verbose=verbose,
                    group=group if distributed else None, rank=rank, local_batch=local_batch)
+        self.overlap_history = []   # S_k of every epoch's walkers (float64 numpy [K] each), when lower_states is in use
+        if penalties is not None:
+            run.lower_states = self._load_lower_states(opt_state.template, opt_state.x.detach().cpu().numpy())
+            run.overlap_penalty, run.overlap_record = penalties, self.overlap_history
+            self.lower_state_models = run.lower_states   # [(psi closure, DeviceParams)]: for measurements against them afterwards
+            run.log_extra = lambda: f" | max |S_k|: {float(np.abs(self.overlap_history[-1]).max()):.4f}" if self.overlap_history else ""
         # the whole step as one captured launch sequence, where the library has it (models the sweeps cover; the wave sampler: <= 131072 walkers
         # per step, no such limit where the staged large-batch sampler applies); otherwise the host-stepped loop (sampler, loss + gradient, Adam: three library calls per step)
         # Sharded over several processes: the same sequence in two halves around the step's one all-reduce.
@@ -588,9 +715,14 @@ class ModelTrainer:
             new_loss = step(epoch, params, batch)
             params = run.get_params(run.opt_state)
             if epoch % self.log_every == 0 and run.verbose:
-                print(f"epoch {epoch} | Loss: {round(float(new_loss), 3)}")
+                print(f"epoch {epoch} | Loss: {round(float(new_loss), 3)}" + (run.log_extra() if getattr(run, "log_extra", None) else ""))
             run.record([new_loss])
         return params
+
+    @staticmethod
+    def _run_overlap_args(run):
+        """The excited-state keywords of the eager steps from what start_training loaded: none without lower states."""
+        return _overlap_args(getattr(run, "lower_states", None), getattr(run, "overlap_penalty", 0.0), getattr(run, "overlap_record", None))
 
     def _train_adam(self, run, group):
         """The host-stepped loop with train_step_efficient (`group` as start_training received it: None means not distributed); the running
@@ -621,7 +753,8 @@ class ModelTrainer:
         """The host-stepped loop with train_step_sr in the place of the Adam step: eager (the solver's status is read every step), parameters on
         the device in opt_state.x, no optimiser state to save."""
         def step(epoch, params, batch):
-            new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}), **self._sr_solver_args())
+            new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}), **self._sr_solver_args(),
+                                                 **self._run_overlap_args(run))
             run.opt_state.x.copy_(new_params.flat)
             run.opt_state.version += 1
             return new_loss
@@ -706,7 +839,7 @@ class ModelTrainer:
 
         def step(epoch, params, batch):
             new_params, d, new_loss = train_step_spring(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, phi, momentum, cap, clip,
-                                                        **self._spring_damping(), **self._sr_solver_args())
+                                                        **self._spring_damping(), **self._sr_solver_args(), **self._run_overlap_args(run))
             capped[0] += int(spring_step_size(_lr_at(self.learning_rate, epoch), d, cap) < float(np.float32(_lr_at(self.learning_rate, epoch))))
             phi.copy_(d)
             run.opt_state.x.copy_(new_params.flat)
