@@ -2,9 +2,10 @@
 stochastic-reconfiguration step it extends (wf_vqmc_sr_step), all captured once in a hipGraph and replayed in the same process:
 
   sr           DeviceModel.sr_step -- the yardstick
-  spring_off   DeviceModel.spring_step with momentum, norm constraint and clip off: the same arithmetic as `sr`, bit for bit
-  spring       DeviceModel.spring_step at --momentum / --norm-constraint / --clip: one more pass over the rows (q = O phi) and the
-               one-workgroup sort of the local energies
+  spring_off   DeviceModel.spring_step with momentum, norm constraint and clip off: the launches of `sr` (one sequence serves both entries)
+               plus phi <- d in the update
+  spring       DeviceModel.spring_step at --momentum / --norm-constraint / --clip: two launches more than `sr` (e_loc ahead of the rows,
+               q = O phi: one more pass over the rows) and the one-workgroup sort of the local energies
 
 and, on their own on the rows of the last step's size (random fp32 [B, n_params]): sr.matvec, sr.apply and sr.apply_add, the passes over the
 rows the step's excess is measured against.  Learning rate 0 by default, as in bench_sr_step.py: the work per step does not drift.  A repeat

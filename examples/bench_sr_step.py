@@ -35,7 +35,9 @@ def launches_per_step(B):
     """Kernel launches of one wf_vqmc_sr_step at B walkers (wave sampler, one chunk of rows), counted from the sequence in DESIGN 4.20."""
     panels = (B + 31) // 32
     solve = 1 + panels + 2 * (panels - 1) + panels          # shift; potrf per panel; trsm + syrk below every panel but the last; back substitution
-    n = {"sampler": 1, "energy": 2, "eloc_rhs": 1, "rows": 3, "gram": 5, "solve": solve, "apply": 3, "verdict_update": 2, "images": 1,
+    # ("rhs": without momentum the one-block right-hand side runs ahead of the rows and computes inv and e_loc itself; a SPRING step with
+    # momentum has three there instead: e_loc, q = O phi, rhs)
+    n = {"sampler": 1, "energy": 2, "rhs": 1, "rows": 3, "gram": 5, "solve": solve, "apply": 3, "verdict_update": 2, "images": 1,
          "ring": 1 if B <= 256 else 2}
     n["total"] = sum(n.values())
     return n

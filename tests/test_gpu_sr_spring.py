@@ -335,13 +335,14 @@ def test_step_with_everything_off_is_the_sr_step_three_particles():
     _off_is_the_old_step(_three(), "D = 3")
 
 
-def _against_the_eager_step(case, tag):
-    """mu = 0.9, clip 5, a previous direction that is not zero and a cap that binds (a tenth of lr^2 |d|^2 of the uncapped step)."""
+def _against_the_eager_step(case, tag, mu=0.9):
+    """mu = 0.9, clip 5, a previous direction that is not zero and a cap that binds (a tenth of lr^2 |d|^2 of the uncapped step).
+    -> a function that runs the device step again from the same start and returns its snapshot."""
     import torch
     from waveflow_amd import core, vqmc
     params, psi, h_fn, x, flat0 = case
     model, B, P = psi.model, int(x.shape[0]), psi.model.n_params
-    mu, clip = 0.9, 5.0
+    clip = 5.0
     phi0 = torch.as_tensor((np.random.default_rng(17).normal(size=P) * 1e-2).astype(np.float32)).cuda()
     dp = core.DeviceParams(params, flat0.clone(), 0)
     d_eager, _ = vqmc.spring_direction(dp, psi, h_fn, x, phi0, mu, clip=clip)
@@ -371,6 +372,13 @@ def _against_the_eager_step(case, tag):
     assert abs(norm[FIRST] - norm2) <= 2.0 ** -20 * norm2
     assert abs(eff_dev - eff) <= 2.0 ** -22 * eff
     assert phi_diff <= P // 100 and bool(torch.isfinite(st["phi"]).all())
+    first = _snapshot(xs, st)
+
+    def again(shifted=False):
+        xs2, st2 = _fresh_state(model, flat0, batch=B, phi=phi0, shifted=shifted)
+        model.spring_step(st2, SEED, B, h_fn.protons, walkers=x, momentum=mu, norm_constraint=cap, clip=clip)
+        return first, _snapshot(xs2, st2)
+    return again
 
 
 def test_step_is_the_eager_step_he(he_flat):
@@ -379,6 +387,14 @@ def test_step_is_the_eager_step_he(he_flat):
 
 def test_step_is_the_eager_step_three_particles():
     _against_the_eager_step(_three(), "D = 3")
+
+
+def test_step_without_momentum_with_clip_and_cap_is_the_eager_step_and_repeatable_he(he_flat):
+    """Momentum 0 with clip 5 and a binding cap: the right-hand side is computed ahead of the rows, with the clamp on (no q to wait for).  Against
+    the eager step under the same bound, and bitwise the same when the step runs again, the workspace at another address."""
+    first, second = _against_the_eager_step(_he(he_flat), "He, momentum 0", mu=0.0)(shifted=True)
+    assert _same(first, second)
+    assert 0.0 < float(first["eff_ring"][FIRST]) < float(np.float32(LR))      # the cap bound
 
 
 @pytest.mark.parametrize("B", RHS_BS)

@@ -101,17 +101,18 @@ def _capture(model, step, restore):
     return graph
 
 
-def _against_the_eager_step(case, tag):
+def _against_the_eager_step(case, tag, moves=True, **damping):
+    """moves=False: a step whose direction is exactly zero (one walker) -- both steps must leave the parameters bitwise as they were."""
     import torch
     from waveflow_amd import core, vqmc
     params, psi, h_fn, x, flat0 = case
     model, B = psi.model, int(x.shape[0])
     dp = core.DeviceParams(params, flat0.clone(), 0)
-    d_eager, _ = vqmc.sr_natural_gradient(dp, psi, h_fn, x)
-    new_dp, loss_eager = vqmc.train_step_sr(1, psi, h_fn, dp, x, LR)
+    d_eager, _ = vqmc.sr_natural_gradient(dp, psi, h_fn, x, **damping)
+    new_dp, loss_eager = vqmc.train_step_sr(1, psi, h_fn, dp, x, LR, **damping)
     assert torch.equal(dp.flat, flat0)
     xs, st = _fresh_state(model, flat0, batch=B)
-    model.sr_step(st, SEED, B, h_fn.protons, walkers=x)
+    model.sr_step(st, SEED, B, h_fn.protons, walkers=x, **damping)
     torch.cuda.synchronize()
     th_s, th_e, d = xs.double().cpu().numpy(), new_dp.flat.double().cpu().numpy(), d_eager.double().cpu().numpy()
     bound = 2.0 ** -23 * np.abs(th_e) + 2.0 ** -22 * LR * np.abs(d)
@@ -122,7 +123,8 @@ def _against_the_eager_step(case, tag):
     want_norm = float((d * d).sum())
     print(f"[sr step vs eager, {tag}] B {B} P {model.n_params}: {n_diff} entries differ (cap {model.n_params // 100}), worst |diff| / bound {worst:.3f}; "
           f"loss {ring[FIRST, 0] / B:.12f} vs {loss_eager:.12f}; |d|^2 {norm[FIRST]:.9e} vs {want_norm:.9e}; status {status}")
-    assert np.isfinite(th_s).all() and not np.array_equal(th_s, flat0.double().cpu().numpy())
+    assert np.isfinite(th_s).all() and np.array_equal(th_s, flat0.double().cpu().numpy()) == (not moves)
+    assert moves or (not d.any() and np.array_equal(th_e, th_s))
     assert (diff <= bound).all()
     assert n_diff <= model.n_params // 100
     assert abs(ring[FIRST, 0] / B - loss_eager) <= 1e-12 * max(1.0, abs(loss_eager)) and ring[FIRST, 2] == B
@@ -138,6 +140,19 @@ def test_step_on_given_walkers_is_the_eager_step_he(he_flat):
 
 def test_step_on_given_walkers_is_the_eager_step_three_particles():
     _against_the_eager_step(_three(), "D = 3")
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_step_on_one_and_two_walkers_is_the_eager_step(he_flat, B):
+    """The smallest batches of the one-block right-hand side.  One walker: the mean is the only entry, the right-hand side and with it d are exactly
+    zero (absolute damping: the centred 1 x 1 matrix is 0, so relative damping alone is refused) and no parameter moves.  Two walkers: the first
+    batch with a direction, under the bound at the head of this file."""
+    params, psi, h_fn, x, flat0 = _he(he_flat)
+    case = (params, psi, h_fn, x[:B].contiguous(), flat0)
+    if B == 1:
+        _against_the_eager_step(case, "He, one walker", moves=False, damping=1e-3)
+    else:
+        _against_the_eager_step(case, "He, two walkers")
 
 
 def test_three_steps_are_bitwise_repeatable_direct_shifted_and_replayed(he_flat):

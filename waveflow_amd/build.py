@@ -9,12 +9,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwaveflow_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
 
-SOURCES = ["wf_tables.cpp", "wf_runtime.cpp", "wf_model_build.cpp", "wf_model_images.cpp", "wf_dispatch.cpp", "wf_train.cpp", "wf_train_sr.cpp", "wf_train_spring.cpp", "wf_train_observe.cpp", "wf_train_dmc.cpp", "wf_kernels_scalar.hip", "wf_scalar_inst_d2.hip", "wf_scalar_inst_d3.hip", "wf_scalar_inst_d4.hip", "wf_scalar_inst_d56.hip",
+SOURCES = ["wf_tables.cpp", "wf_runtime.cpp", "wf_model_build.cpp", "wf_model_images.cpp", "wf_dispatch.cpp", "wf_train.cpp", "wf_train_sr.cpp", "wf_train_observe.cpp", "wf_train_dmc.cpp", "wf_kernels_scalar.hip", "wf_scalar_inst_d2.hip", "wf_scalar_inst_d3.hip", "wf_scalar_inst_d4.hip", "wf_scalar_inst_d56.hip",
            "wf_scalar_inst_d78.hip", "wf_scalar_inst_n64.hip", "wf_scalar_inst_n64_d56.hip",
            "wf_scalar_inst_n64_d78.hip", "wf_kernels_mfma.hip", "wf_mfma_inst_d2.hip", "wf_mfma_inst_d2t2.hip", "wf_mfma_inst_d34.hip",
            "wf_mfma_inst_d567.hip", "wf_mfma_inst_d8.hip", "wf_mfma_inst_k2.hip", "wf_kernels_rqs.hip", "wf_kernels_grad.hip", "wf_kernels_wave.hip", "wf_kernels_etile.hip",
            "wf_kernels_etile_bwd.hip", "wf_etile_bwd_k2.hip", "wf_kernels_etile_sample.hip", "wf_kernels_etile_dir.hip", "wf_kernels_spline.hip",
-           "wf_kernels_sr.hip", "wf_kernels_sr_step.hip", "wf_kernels_sr_spring.hip", "wf_kernels_sr_cg.hip", "wf_kernels_observe.hip", "wf_kernels_dmc.hip",
+           "wf_kernels_sr.hip", "wf_kernels_sr_step.hip", "wf_kernels_sr_cg.hip", "wf_kernels_observe.hip", "wf_kernels_dmc.hip",
            "wf_train_dmc_observe.cpp", "wf_kernels_dmc_observe.hip", "wf_train_overlap.cpp", "wf_kernels_overlap.hip"]
 # -ffp-contract=off: the index arithmetic and the table lerp keep the reference's separate
 # multiply / add roundings; dot products that may fuse say so with explicit fmaf / MFMA.

@@ -281,21 +281,17 @@ int64_t block_sums_ws_bytes(int64_t B);
 constexpr int kModePresort = 4;   // bit of launch_mfma's mode: sort each row in registers, psi gets (-1)^inversions (wf_mfma_impl.h)
 int launch_sort_rows(const float* x, int64_t B, int D, float* xs, int32_t* inv, void* stream);
 int launch_apply_sign(float* v, const int32_t* inv, int64_t B, void* stream);
-// the glue of wf_vqmc_sr_step (wf_kernels_sr_step.hip): inv = 1 / (psi + 1e-8), e_loc = hpsi inv, rhs = e_loc - mean(e_loc) in fp64 (B <= 4096);
-// |d|^2 in fp64 with the step's verdict (flag[0] = 1: update; status and norm ring as include/waveflow_sr_step.h); the guarded update
-int launch_sr_eloc_rhs(const float* hpsi, const float* psi, int64_t B, float* e_loc, float* inv, double* rhs, void* stream);
-int launch_sr_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, int ring_len,
-                      const unsigned long long* counter, void* stream);
-int launch_sr_update(float* params, const float* d, int64_t P, const float* step_size, const int32_t* flag, void* stream);
-// the glue of wf_vqmc_spring_step (wf_kernels_sr_spring.hip): inv and e_loc ahead of the rows; the clipped, momentum-corrected and centred right-hand
-// side (B <= 4096; stats[4] = median, mean absolute deviation, the two clamp bounds); the verdict of k_sr_verdict with the capped step size
-// (eff[0], eff_ring: 0 for a skipped step); the guarded update of theta and phi
-int launch_spring_eloc(const float* hpsi, const float* psi, int64_t B, float* e_loc, float* inv, void* stream);
-int launch_spring_rhs(const float* hpsi, const float* psi, int64_t B, const double* q, double mu, double clip, float* e_loc, float* inv, double* rhs,
-                      double* stats, void* stream);
-int launch_spring_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, double* eff_ring, int ring_len,
-                          const unsigned long long* counter, const float* step_size, double cap, float* eff, void* stream);
-int launch_spring_update(float* params, float* phi, const float* d, int64_t P, const float* eff, const int32_t* flag, void* stream);
+// the glue of the stochastic-reconfiguration step, plain and SPRING (wf_kernels_sr_step.hip; the step: wf_train_sr.cpp): inv = 1 / (psi + 1e-8) and
+// e_loc = hpsi inv ahead of the rows; the same two with the clipped, momentum-corrected and centred right-hand side in fp64 (B <= 4096; q may be null
+// when mu == 0; stats[4], which may be null = median, mean absolute deviation, the two clamp bounds; mu = clip = 0: rhs = e_loc - mean(e_loc)); |d|^2
+// in fp64 with the step's verdict (flag[0] = 1: update; status and norm ring as include/waveflow_sr_step.h) and the capped step size (eff[0], and
+// eff_ring where there is one: 0 for a skipped step; cap = 0: eff = step_size[0]); the guarded update of theta and, where it is not null, phi
+int launch_sr_eloc(const float* hpsi, const float* psi, int64_t B, float* e_loc, float* inv, void* stream);
+int launch_sr_rhs(const float* hpsi, const float* psi, int64_t B, const double* q, double mu, double clip, float* e_loc, float* inv, double* rhs,
+                  double* stats, void* stream);
+int launch_sr_verdict(const float* d, int64_t P, const int32_t* info, int32_t* status, int32_t* flag, double* norm_ring, double* eff_ring, int ring_len,
+                      const unsigned long long* counter, const float* step_size, double cap, float* eff, void* stream);
+int launch_sr_update(float* params, float* phi, const float* d, int64_t P, const float* eff, const int32_t* flag, void* stream);
 
 void set_hip_error(int e);
 

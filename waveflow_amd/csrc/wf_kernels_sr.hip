@@ -2,6 +2,9 @@
 //     Tbar = H (O O^T) H / B        wf_sr_gram    fp64 matrix cores, P split into chunks, fixed-order reduce, centring on the B x B matrix
 //     (Tbar + lambda I) y = rhs     wf_sr_solve   blocked right-looking Cholesky (32-column panels), forward solve fused into the panels
 //     out = scale O^T (H y)         wf_sr_apply   one pass over the rows, fp64 slab partials, fixed-order reduce
+// and the two row passes SPRING (include/waveflow_sr_spring.h) adds:
+//     q = O v                       wf_sr_matvec      one pass over the rows, fp64, one workgroup per row
+//     out = mu prev + scale O^T (H y)   wf_sr_apply_add   the same apply: its reduce adds mu prev before its one rounding (wf_sr_apply: no prev)
 // Model-free, like wf_adam_step: kernels and their host entry points live in this one unit.  Nothing here adds with atomics, and every
 // sum has one order that depends on (B, P) alone: the three results are bitwise reproducible.
 //
@@ -15,7 +18,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/waveflow_sr.h"
+#include "../../include/waveflow_sr_spring.h"
 #include "wf_internal.h"
 #include "wf_sr_common.h"
 
@@ -399,13 +402,52 @@ __global__ __launch_bounds__(256) void k_sr_apply(const float* __restrict__ rows
     if (c + 3 < P) out[3] = a3;
 }
 
-// out[p] = (float)(scale * sum of the slab partials, slab 0 first)
-__global__ __launch_bounds__(256) void k_sr_apply_reduce(const double* __restrict__ partial, int64_t nslab, int64_t P, double scale, float* __restrict__ out) {
+// out[p] = (float)(mu prev[p] + scale * sum of the slab partials, slab 0 first); prev == nullptr or mu == 0: (float)(scale * sum).  out may be prev.
+__global__ __launch_bounds__(256) void k_sr_apply_add_reduce(const double* __restrict__ partial, int64_t nslab, int64_t P, double scale, const float* prev, double mu,
+                                                             float* out) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     double s = 0.0;
     for (int64_t i = 0; i < nslab; ++i) s += partial[i * P + p];
-    out[p] = (float)(scale * s);
+    double v = scale * s;
+    if (prev != nullptr && mu != 0.0) v = mu * (double)prev[p] + v;
+    out[p] = (float)v;
+}
+
+// the three launches of wf_sr_apply and wf_sr_apply_add (arguments checked by the entries)
+static int sr_apply(const float* rows, int64_t B, int64_t P, int64_t ld, const double* y, double scale, const float* prev, double mu, float* out, void* ws,
+                    void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    double* yc = (double*)ws;
+    double* partial = (double*)((char*)ws + sr_align(B * 8));
+    const int64_t nslab = (B + kSrSlab - 1) / kSrSlab;
+    hipLaunchKernelGGL(k_sr_ycentre, dim3(1), dim3(256), 0, s, y, B, yc);
+    hipLaunchKernelGGL(k_sr_apply, dim3((unsigned)((P + 1023) / 1024), (unsigned)nslab), dim3(256), 0, s, rows, ld, B, P, (int)sr_vec_ok(rows, ld),
+                       (const double*)yc, partial);
+    hipLaunchKernelGGL(k_sr_apply_add_reduce, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const double*)partial, nslab, P, scale, prev, mu, out);
+    return sr_finish();
+}
+
+// ---- matvec
+
+// q[b] = sum_p rows[b][p] v[p]: one workgroup per row; thread t takes columns 4 t .. 4 t + 3, then + 1024, ... into four fp64 sums (one per
+// column of its group, every product exact in fp64), ((s0 + s1) + (s2 + s3)), then the tree over the 256 threads
+__global__ __launch_bounds__(256) void k_sr_matvec(const float* __restrict__ rows, int64_t ld, int64_t B, int64_t P, int vec, const float* __restrict__ v, int vvec,
+                                                   double* __restrict__ q) {
+    __shared__ double red[256];
+    const int64_t b = blockIdx.x;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll 4
+    for (int64_t c = (int64_t)threadIdx.x * 4; c < P; c += 4 * 256) {
+        const float4 r = sr_load4(rows, ld, b, B, c, P, vec != 0);
+        const float4 w = sr_load4(v, 0, 0, 1, c, P, vvec != 0);
+        s0 += (double)r.x * (double)w.x;
+        s1 += (double)r.y * (double)w.y;
+        s2 += (double)r.z * (double)w.z;
+        s3 += (double)r.w * (double)w.w;
+    }
+    const double s = sr_block_sum((s0 + s1) + (s2 + s3), red);
+    if (threadIdx.x == 0) q[b] = s;
 }
 
 }  // namespace wf
@@ -470,14 +512,25 @@ int wf_sr_apply(const float* rows_dev, int64_t B, int64_t P, int64_t ld, const d
     if (B > kSrMaxRows) return WF_ERR_UNSUPPORTED;
     if (workspace_bytes < apply_ws_bytes(B, P)) return WF_ERR_INVALID;
     if (wf_device_count() <= 0) return WF_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    double* yc = (double*)workspace_dev;
-    double* partial = (double*)((char*)workspace_dev + sr_align(B * 8));
-    const int64_t nslab = (B + kSrSlab - 1) / kSrSlab;
-    hipLaunchKernelGGL(k_sr_ycentre, dim3(1), dim3(256), 0, s, y_dev, B, yc);
-    hipLaunchKernelGGL(k_sr_apply, dim3((unsigned)((P + 1023) / 1024), (unsigned)nslab), dim3(256), 0, s, rows_dev, ld, B, P, (int)sr_vec_ok(rows_dev, ld),
-                       yc, partial);
-    hipLaunchKernelGGL(k_sr_apply_reduce, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const double*)partial, nslab, P, scale, out_dev);
+    return sr_apply(rows_dev, B, P, ld, y_dev, scale, nullptr, 0.0, out_dev, workspace_dev, stream);
+}
+
+int wf_sr_apply_add(const float* rows_dev, int64_t B, int64_t P, int64_t ld, const double* y_dev, double scale, const float* prev_dev, double mu,
+                    float* out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+    if (B < 1 || P < 1 || ld < P || !rows_dev || !y_dev || !out_dev || !workspace_dev) return WF_ERR_INVALID;
+    if (!(mu >= 0.0) || !(mu < 1.0)) return WF_ERR_INVALID;
+    if (B > kSrMaxRows) return WF_ERR_UNSUPPORTED;
+    if (workspace_bytes < apply_ws_bytes(B, P)) return WF_ERR_INVALID;
+    if (wf_device_count() <= 0) return WF_ERR_NO_DEVICE;
+    return sr_apply(rows_dev, B, P, ld, y_dev, scale, prev_dev, mu, out_dev, workspace_dev, stream);
+}
+
+int wf_sr_matvec(const float* rows_dev, int64_t B, int64_t P, int64_t ld, const float* v_dev, double* q_dev, void* stream) {
+    if (B < 1 || P < 1 || ld < P || !rows_dev || !v_dev || !q_dev) return WF_ERR_INVALID;
+    if (B > kSrMaxRows) return WF_ERR_UNSUPPORTED;
+    if (wf_device_count() <= 0) return WF_ERR_NO_DEVICE;
+    hipLaunchKernelGGL(k_sr_matvec, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rows_dev, ld, B, P, (int)sr_vec_ok(rows_dev, ld), v_dev,
+                       (int)sr_vec_ok(v_dev, 0), q_dev);
     return sr_finish();
 }
 

@@ -174,15 +174,4 @@ int run_vjp_chunks(const wf_model* m, int mode, bool second_order, const float* 
                    const Protons* pr, float running_average, float inv_count, float* e_loc_dev, float* grad_dev, void* workspace_dev,
                    int64_t workspace_bytes, void* stream, const float* running_average_dev = nullptr, int* defer_gather_split = nullptr);
 
-// ---- wf_train_sr.cpp: what wf_vqmc_sr_step and wf_vqmc_spring_step (wf_train_spring.cpp) share -- the batch limit of wf_sr_solve, the models
-// they cover, and the workspace: fixed-size vectors, rows, the batch x batch matrix, the workspace of waveflow_sr.h, and one area the sampler
-// (staged form only), the energy sweep and the tape of wf_psi_jac use one after the other.  q [batch] fp64 exists only `with_q` (SPRING).
-constexpr int64_t kSrStepMaxBatch = 4096;
-struct SrStepLayout {
-    int64_t x, hpsi, psi, e_loc, inv, rhs, y, q, d, scalars, sums_ws, rows, t, sr, tape;   // offsets
-    int64_t sr_bytes, tape_bytes, total;
-};
-bool sr_step_covered(const wf_model* m);
-SrStepLayout sr_step_layout(const wf_model* m, int64_t batch, bool with_q);
-
 }  // namespace wf

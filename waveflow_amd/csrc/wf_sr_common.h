@@ -1,6 +1,5 @@
-// wf_sr_common.h -- what wf_kernels_sr.hip, wf_kernels_sr_step.hip, wf_kernels_sr_spring.hip and wf_kernels_sr_cg.hip share: the launch check, the block sum, the
-// predicated 4-column load of the rows, the test for 16-byte loads, the slab pass of the apply (defined in wf_kernels_sr.hip, launched from
-// there and from wf_kernels_sr_spring.hip) and the workspace it needs.
+// wf_sr_common.h -- what wf_kernels_sr.hip, wf_kernels_sr_step.hip and wf_kernels_sr_cg.hip share: the launch check, the block sum, the
+// predicated 4-column load of the rows, the test for 16-byte loads and the workspace of the apply.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,10 +54,5 @@ __device__ __forceinline__ float4 sr_load4(const float* __restrict__ rows, int64
     if (c + 3 < c_end) v.w = p[3];
     return v;
 }
-
-// yc = y - mean y (one block); partial[slab][p] = sum over the 32 rows of the slab, first row first, of yc[b] rows[b][p]
-__global__ void k_sr_ycentre(const double* __restrict__ y, int64_t B, double* __restrict__ yc);
-__global__ void k_sr_apply(const float* __restrict__ rows, int64_t ld, int64_t B, int64_t P, int vec, const double* __restrict__ yc,
-                           double* __restrict__ partial);
 
 }  // namespace wf

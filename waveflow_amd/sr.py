@@ -276,25 +276,11 @@ def natural_gradient(rows, e_loc, damping=0.0, relative_damping=1e-3, solver='ch
     lambda = damping + relative_damping * trace(Tbar) / B -> float32 cuda [P].  Three library calls on the current stream, then one read of the
     solver's status: NotPositiveDefinite if a pivot was not positive.  solver='cg': Tbar is never formed and B may exceed MAX_WALKERS -- solve_cg
     to `tol` within `max_iter` iterations (NotConverged, NotFinite), then the same apply."""
-    import torch
     damping, relative_damping = _check_damping(damping, relative_damping)
     solver, tol, max_iter, _ = _check_solver(solver, tol, max_iter)
     B, P, ld = _check_rows(rows, limit=MAX_WALKERS if solver == 'cholesky' else MAX_ROWS)
     _check_vector(e_loc, B, None, "e_loc", rows.device)
-    if solver == 'cg':
-        ws = _cg_workspace(B, P, rows.device)
-        e = e_loc.double()
-        y, _ = _solve_cg(rows, B, P, ld, e - e.mean(), damping, relative_damping, tol, max_iter, 32, False, ws)
-        return _apply(rows, B, P, ld, y, 2.0 / B, ws)
-    ws = _workspace(B, P, rows.device)
-    T = _gram(rows, B, P, ld, ws)
-    e = e_loc.double()
-    y, info = _solve(T, B, e - e.mean(), damping, relative_damping, ws)
-    d = _apply(rows, B, P, ld, y, 2.0 / B, ws)
-    pivot = int(info.item())
-    if pivot != 0:
-        raise NotPositiveDefinite(pivot)
-    return d
+    return _direction(rows, B, P, ld, e_loc.double(), None, 0.0, damping, relative_damping, solver, tol, max_iter)
 
 
 # ---- SPRING (include/waveflow_sr_spring.h)
@@ -400,20 +386,26 @@ def spring_direction(rows, e_loc, prev, momentum, damping=0.0, relative_damping=
     B, P, ld = _check_rows(rows, limit=MAX_WALKERS if solver == 'cholesky' else MAX_ROWS)
     _check_vector(e_loc, B, None, "e_loc", rows.device)
     _check_vector(prev, P, torch.float32, "prev", rows.device)
-    prev = prev.contiguous()
+    return _direction(rows, B, P, ld, clip_local_energies(e_loc, clip), prev.contiguous(), momentum, damping, relative_damping, solver, tol, max_iter)
+
+
+def _direction(rows, B, P, ld, e, prev, mu, damping, relative_damping, solver, tol, max_iter):
+    """d = mu prev + (2 / B) O^T H y with (Tbar + lambda I) y = H (e - (mu / 2) O prev) for checked operands: e float64 [B], not centred; prev None
+    (then mu is 0): the plain natural gradient.  The dense workspace, Gram matrix and Cholesky solve with its pivot check, or solver='cg'."""
+    import torch
     ws = _workspace(B, P, rows.device) if solver == 'cholesky' else _cg_workspace(B, P, rows.device)
-    r = clip_local_energies(e_loc, clip)
-    if momentum != 0.0:
-        r = r - (0.5 * momentum) * _matvec(rows, B, P, ld, prev)
+    r = e if mu == 0.0 else e - (0.5 * mu) * _matvec(rows, B, P, ld, prev)
+    info = None
     if solver == 'cg':
         y, _ = _solve_cg(rows, B, P, ld, r - r.mean(), damping, relative_damping, tol, max_iter, 32, False, ws)
-        return _apply_add(rows, B, P, ld, y, 2.0 / B, prev, momentum, torch.empty(P, dtype=torch.float32, device=rows.device), ws)
-    T = _gram(rows, B, P, ld, ws)
-    y, info = _solve(T, B, r - r.mean(), damping, relative_damping, ws)
-    d = _apply_add(rows, B, P, ld, y, 2.0 / B, prev, momentum, torch.empty(P, dtype=torch.float32, device=rows.device), ws)
-    pivot = int(info.item())
-    if pivot != 0:
-        raise NotPositiveDefinite(pivot)
+    else:
+        y, info = _solve(_gram(rows, B, P, ld, ws), B, r - r.mean(), damping, relative_damping, ws)
+    if prev is None:
+        d = _apply(rows, B, P, ld, y, 2.0 / B, ws)
+    else:
+        d = _apply_add(rows, B, P, ld, y, 2.0 / B, prev, mu, torch.empty(P, dtype=torch.float32, device=rows.device), ws)
+    if info is not None and int(info.item()) != 0:
+        raise NotPositiveDefinite(int(info.item()))
     return d
 
 

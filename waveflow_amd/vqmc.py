@@ -298,6 +298,27 @@ def _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_reco
     return e_pen
 
 
+def _sr_rows_and_energies(what, params, psi, h_fn, batch, damping, relative_damping, group, solver, tol, max_iter, lower_states, overlap_penalty,
+                          overlap_record, spring=None):
+    """What sr_natural_gradient and spring_direction share ahead of the solve: the checks (spring: (momentum, clip) for SPRING), then on the
+    walkers of `batch` the rows O = d psi / d theta / (psi + 1e-8), the local energies e_loc = H psi / (psi + 1e-8) and the energies the solver
+    receives (penalised when there are lower states, else e_loc itself) -> (rows, e_used, e_loc)."""
+    from . import sr
+    lower_states, penalty = _check_lower_states(lower_states, overlap_penalty)
+    if group is not None:
+        raise NotImplementedError(f"{what} over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
+    sr._check_damping(damping, relative_damping)
+    if spring is not None:
+        sr._check_spring(spring[0], 0.0, spring[1])
+    sr._check_solver(solver, tol, max_iter)
+    model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
+    inv = 1.0 / (ps + 1e-8)
+    e_loc = hpsi * inv
+    rows = model.psi_jacobian(x, w_psi=inv)
+    e_used = _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_record) if lower_states else e_loc
+    return rows, e_used, e_loc
+
+
 def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=1e-3, group=None, solver='cholesky', tol=1e-8, max_iter=2000, *,
                         lower_states=None, overlap_penalty=0.0, overlap_record=None):
     """Stochastic reconfiguration on the walkers of `batch`: d = (S + lambda I)^-1 g with O_k(x_b) = d ln psi_b / d theta_k (the rows of
@@ -313,16 +334,8 @@ def sr_natural_gradient(params, psi, h_fn, batch, damping=0.0, relative_damping=
     this step's walkers (float64 numpy [K]) -- how every function of this module that takes lower_states reports the overlaps; the return
     values keep their shape.  With lower_states None or empty nothing of this is called and the result is bit for bit the one without."""
     from . import sr
-    lower_states, penalty = _check_lower_states(lower_states, overlap_penalty)
-    if group is not None:
-        raise NotImplementedError("stochastic reconfiguration over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
-    sr._check_damping(damping, relative_damping)
-    sr._check_solver(solver, tol, max_iter)
-    model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
-    inv = 1.0 / (ps + 1e-8)
-    e_loc = hpsi * inv
-    rows = model.psi_jacobian(x, w_psi=inv)
-    e_used = _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_record) if lower_states else e_loc
+    rows, e_used, e_loc = _sr_rows_and_energies("stochastic reconfiguration", params, psi, h_fn, batch, damping, relative_damping, group, solver, tol, max_iter,
+                                                lower_states, overlap_penalty, overlap_record)
     d = sr.natural_gradient(rows, e_used, damping=damping, relative_damping=relative_damping, **_solver_args(solver, tol, max_iter))
     return d, float(e_loc.double().mean())
 
@@ -337,17 +350,21 @@ def _overlap_args(lower_states, overlap_penalty, overlap_record):
     return {"lower_states": lower_states, "overlap_penalty": overlap_penalty, "overlap_record": overlap_record} if lower_states else {}
 
 
+def _stepped(params, step, d):
+    """params - step * d as a new pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one; `params` is left as it is."""
+    if isinstance(params, DeviceParams):
+        return DeviceParams(params.template, params.flat - step * d.to(params.flat.device), params.version + 1)
+    flat = flatten_params(params).astype(np.float32)
+    return checkpoint.unflatten_like(params, flat - np.float32(step) * d.cpu().numpy())
+
+
 def train_step_sr(epoch, psi, h_fn, params, batch, learning_rate, group=None, *, lower_states=None, overlap_penalty=0.0, overlap_record=None, **damping):
     """One stochastic-reconfiguration step theta <- theta - lr d (sr_natural_gradient; `damping`: its damping / relative_damping, and solver / tol / max_iter;
     learning_rate: a number, or a schedule called with `epoch`) -> (new params, loss).  `params` is left as it is: the result is a new
     pytree of the same shape (numpy leaves), or a new core.DeviceParams when `params` is one.  lower_states, overlap_penalty, overlap_record:
     as in sr_natural_gradient."""
     d, loss_val = sr_natural_gradient(params, psi, h_fn, batch, group=group, **damping, **_overlap_args(lower_states, overlap_penalty, overlap_record))
-    lr = _lr_at(learning_rate, epoch)
-    if isinstance(params, DeviceParams):
-        return DeviceParams(params.template, params.flat - lr * d.to(params.flat.device), params.version + 1), loss_val
-    flat = flatten_params(params).astype(np.float32)
-    return checkpoint.unflatten_like(params, flat - np.float32(lr) * d.cpu().numpy()), loss_val
+    return _stepped(params, _lr_at(learning_rate, epoch), d), loss_val
 
 
 def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, relative_damping=1e-3, clip=0.0, group=None, solver='cholesky', tol=1e-8,
@@ -358,17 +375,8 @@ def spring_direction(params, psi, h_fn, batch, prev, momentum, damping=0.0, rela
     Sharded walkers (`group`) are not supported.  solver, tol, max_iter: as in sr_natural_gradient.  lower_states, overlap_penalty,
     overlap_record: as in sr_natural_gradient -- the clip then clamps the penalised energies around their median."""
     from . import sr
-    lower_states, penalty = _check_lower_states(lower_states, overlap_penalty)
-    if group is not None:
-        raise NotImplementedError("SPRING over sharded walkers (group=...) is not implemented: pass all walkers on one GPU")
-    sr._check_damping(damping, relative_damping)
-    sr._check_spring(momentum, 0.0, clip)
-    sr._check_solver(solver, tol, max_iter)
-    model, x, hpsi, ps, _ = _energy_terms(params, psi, h_fn, batch)
-    inv = 1.0 / (ps + 1e-8)
-    e_loc = hpsi * inv
-    rows = model.psi_jacobian(x, w_psi=inv)
-    e_used = _penalised_energies(model, x, ps, e_loc, lower_states, penalty, overlap_record) if lower_states else e_loc
+    rows, e_used, e_loc = _sr_rows_and_energies("SPRING", params, psi, h_fn, batch, damping, relative_damping, group, solver, tol, max_iter, lower_states,
+                                                overlap_penalty, overlap_record, spring=(momentum, clip))
     d = sr.spring_direction(rows, e_used, prev.to(rows.device), momentum, damping=damping, relative_damping=relative_damping, clip=clip,
                             **_solver_args(solver, tol, max_iter))
     return d, float(e_loc.double().mean())
@@ -393,10 +401,7 @@ def train_step_spring(epoch, psi, h_fn, params, batch, learning_rate, prev, mome
     d, loss_val = spring_direction(params, psi, h_fn, batch, prev, momentum, clip=clip, group=group, **damping,
                                    **_overlap_args(lower_states, overlap_penalty, overlap_record))
     eff = spring_step_size(_lr_at(learning_rate, epoch), d, norm_constraint)
-    if isinstance(params, DeviceParams):
-        return DeviceParams(params.template, params.flat - eff * d.to(params.flat.device), params.version + 1), d, loss_val
-    flat = flatten_params(params).astype(np.float32)
-    return checkpoint.unflatten_like(params, flat - np.float32(eff) * d.cpu().numpy()), d, loss_val
+    return _stepped(params, eff, d), d, loss_val
 
 
 def _save_spring_state(save_dir, phi, epoch):
@@ -750,67 +755,16 @@ class ModelTrainer:
         return {"solver": solver}
 
     def _train_sr(self, run):
-        """The host-stepped loop with train_step_sr in the place of the Adam step: eager (the solver's status is read every step), parameters on
-        the device in opt_state.x, no optimiser state to save."""
-        def step(epoch, params, batch):
-            new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}), **self._sr_solver_args(),
-                                                 **self._run_overlap_args(run))
-            run.opt_state.x.copy_(new_params.flat)
-            run.opt_state.version += 1
-            return new_loss
-        return self._train_host(run, step, save_optimizer=False)
+        return self._train_sr_eager(run, spring=False)
 
     def _train_sr_device(self, run):
-        """optimizer='sr' with sr_on_device: run_device_loop around wf_vqmc_sr_step.  Per epoch one graph launch (use_graph) or one library call;
-        the learning rate is a device scalar, rewritten before the step when `learning_rate` is a schedule; the host looks at the loss ring every
-        100 epochs and at checkpoints, and at the step's status with it: steps the solver refused (a pivot that is not positive, a step that is not
-        finite) leave the parameters as they are and are reported once, with their count."""
-        import warnings
-        model, opt_state, start_epoch = run.psi.model, run.opt_state, run.start_epoch
-        lr = self.learning_rate
-        damping = getattr(self, "sr_damping", {})
-        batch = int(self.batch_size)
-        st = model.make_sr_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True)
-        model.set_params_device(opt_state.x)
-        seed = int(run.rng.integers(1 << 62))
+        return self._train_sr_on_device(run, spring=False)
 
-        def step():
-            model.sr_step(st, seed, batch, run.h_fn.protons, exact_sampler=self.exact_sampler, **damping)
-        st["ws"] = model._workspace(model.sr_step_workspace_bytes(batch), opt_state.x.device)   # allocated here, outside the capture
+    def _train_spring(self, run):
+        return self._train_sr_eager(run, spring=True)
 
-        def warm_up():
-            # one step outside the capture (every kernel of the sequence has run once before it is recorded) at learning rate 0: the
-            # parameters come out bitwise as they went in; what it left in the counter, the rings and the status is put back
-            step()
-            st["counter"].fill_(start_epoch + 1)
-            for name in ("ring", "norm_ring", "status"):
-                st[name].zero_()
-        launch = capture_step(model, step, warm_up, "hipGraph capture of the stochastic-reconfiguration step failed") if self.use_graph else step
-        if callable(lr):   # a schedule: the rate of its epoch in front of every step
-            epochs = iter(range(start_epoch + 1, start_epoch + self.num_epochs + 1))
-
-            def replay():
-                st["step_size"].fill_(_lr_at(lr, next(epochs)))
-                launch()
-        else:
-            st["step_size"].fill_(float(lr))
-            replay = launch
-        warned = [False]
-
-        def status(upto):
-            info, skipped = (int(v) for v in st["status"].cpu().tolist())
-            if skipped and not warned[0]:
-                warned[0] = True
-                warnings.warn(f"stochastic reconfiguration: {skipped} of the first {upto - start_epoch} steps were skipped (status of the last step: "
-                              f"{info}; > 0: that pivot of the shifted B x B matrix is not positive, -1: the step is not finite) -- more damping")
-
-        def fetched(epoch, new):
-            run.record(new)
-            if epoch % self.log_every == 0 and run.verbose:
-                print(f"epoch {epoch} | Loss: {round(float(new[-1]), 3)}")
-        return run_device_loop(model, opt_state, run.get_params, replay, loss_ring_reader(model, st, start_epoch + 1, after=status), run.record,
-                               start_epoch + 1, start_epoch + self.num_epochs, self.log_every,
-                               lambda epoch, params: run.checkpoint(int(run.rng.integers(1 << 31)), epoch, params, False), 100, fetched)
+    def _train_spring_device(self, run):
+        return self._train_sr_on_device(run, spring=True)
 
     def _spring_damping(self):
         return getattr(self, "sr_damping", None) or {"relative_damping": SPRING_DEFAULTS["relative_damping"]}
@@ -830,56 +784,74 @@ class ModelTrainer:
         run.save_extra = lambda epoch: _save_spring_state(run.save_dir, phi, epoch)
         return phi
 
-    def _train_spring(self, run):
-        """The host-stepped loop with train_step_spring: eager, parameters in opt_state.x, the previous direction carried from step to step and saved
-        with every checkpoint.  At the end the number of steps the norm cap bound is reported (self.spring_capped_steps)."""
-        momentum, cap, clip = self._spring_settings()
-        phi = self._spring_phi(run)
+    def _train_sr_eager(self, run, spring):
+        """The host-stepped loop with train_step_sr, or with spring: train_step_spring, in the place of the Adam step: eager (the solver's status is
+        read every step), parameters on the device in opt_state.x, no optimiser state to save.  SPRING carries the previous direction from step to
+        step, saves it with every checkpoint and reports at the end the number of steps the norm cap bound (self.spring_capped_steps)."""
+        if spring:
+            momentum, cap, clip = self._spring_settings()
+            phi = self._spring_phi(run)
         capped = [0]
 
         def step(epoch, params, batch):
-            new_params, d, new_loss = train_step_spring(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, phi, momentum, cap, clip,
-                                                        **self._spring_damping(), **self._sr_solver_args(), **self._run_overlap_args(run))
-            capped[0] += int(spring_step_size(_lr_at(self.learning_rate, epoch), d, cap) < float(np.float32(_lr_at(self.learning_rate, epoch))))
-            phi.copy_(d)
+            if spring:
+                new_params, d, new_loss = train_step_spring(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, phi, momentum, cap, clip,
+                                                            **self._spring_damping(), **self._sr_solver_args(), **self._run_overlap_args(run))
+                capped[0] += int(spring_step_size(_lr_at(self.learning_rate, epoch), d, cap) < float(np.float32(_lr_at(self.learning_rate, epoch))))
+                phi.copy_(d)
+            else:
+                new_params, new_loss = train_step_sr(epoch, run.psi, run.h_fn, params, batch, self.learning_rate, **getattr(self, "sr_damping", {}),
+                                                     **self._sr_solver_args(), **self._run_overlap_args(run))
             run.opt_state.x.copy_(new_params.flat)
             run.opt_state.version += 1
             return new_loss
         params = self._train_host(run, step, save_optimizer=False)
-        self.spring_capped_steps, self.spring_skipped_steps = capped[0], 0
-        if run.verbose:
-            print(f"SPRING: the norm constraint bound {capped[0]} of {self.num_epochs} steps")
+        if spring:
+            self.spring_capped_steps, self.spring_skipped_steps = capped[0], 0
+            if run.verbose:
+                print(f"SPRING: the norm constraint bound {capped[0]} of {self.num_epochs} steps")
         return params
 
-    def _train_spring_device(self, run):
-        """optimizer='spring' with sr_on_device: run_device_loop around wf_vqmc_spring_step, exactly as _train_sr_device around wf_vqmc_sr_step.  With
-        the loss ring the host reads the step's status and the ring of applied step sizes: skipped steps are reported once, with their count; the
-        steps the norm cap bound are counted (self.spring_capped_steps) and reported at the end with the skipped ones."""
+    def _train_sr_on_device(self, run, spring):
+        """optimizer='sr' or, with spring, 'spring' under sr_on_device: run_device_loop around wf_vqmc_sr_step / wf_vqmc_spring_step.  Per epoch one
+        graph launch (use_graph) or one library call; the learning rate is a device scalar, rewritten before the step when `learning_rate` is a
+        schedule; the host looks at the loss ring every 100 epochs and at checkpoints, and at the step's status with it: steps the solver refused
+        (a pivot that is not positive, a step that is not finite) leave the parameters as they are and are reported once, with their count.
+        SPRING also reads the ring of applied step sizes there: the steps the norm cap bound are counted (self.spring_capped_steps) and reported
+        at the end with the skipped ones."""
         import warnings
         model, opt_state, start_epoch = run.psi.model, run.opt_state, run.start_epoch
         lr = self.learning_rate
-        damping = self._spring_damping()
-        momentum, cap, clip = self._spring_settings()
         batch = int(self.batch_size)
-        phi = self._spring_phi(run)
-        st = model.make_spring_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True, phi=phi)
+        name, step_name = ("SPRING", "SPRING") if spring else ("stochastic reconfiguration", "stochastic-reconfiguration")
+        if spring:
+            momentum, cap, clip = self._spring_settings()
+            settings = dict(self._spring_damping(), momentum=momentum, norm_constraint=cap, clip=clip)
+            phi = self._spring_phi(run)
+            st = model.make_spring_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True, phi=phi)
+            run_step, ws_bytes, rings = model.spring_step, model.spring_step_workspace_bytes, ("ring", "norm_ring", "eff_ring", "status")
+        else:
+            settings = getattr(self, "sr_damping", {})
+            st = model.make_sr_train_state(opt_state.x, start_epoch + 1, 0.0, ring_len=128, defer_eval_tables=True)
+            run_step, ws_bytes, rings = model.sr_step, model.sr_step_workspace_bytes, ("ring", "norm_ring", "status")
         model.set_params_device(opt_state.x)
         seed = int(run.rng.integers(1 << 62))
 
         def step():
-            model.spring_step(st, seed, batch, run.h_fn.protons, exact_sampler=self.exact_sampler, momentum=momentum, norm_constraint=cap, clip=clip, **damping)
-        st["ws"] = model._workspace(model.spring_step_workspace_bytes(batch), opt_state.x.device)   # allocated here, outside the capture
-        phi0 = phi.clone()
+            run_step(st, seed, batch, run.h_fn.protons, exact_sampler=self.exact_sampler, **settings)
+        st["ws"] = model._workspace(ws_bytes(batch), opt_state.x.device)   # allocated here, outside the capture
+        phi0 = phi.clone() if spring else None
 
         def warm_up():
-            # one step outside the capture at learning rate 0: the parameters come out bitwise as they went in; the direction it left in phi,
-            # the counter, the rings and the status are put back
+            # one step outside the capture (every kernel of the sequence has run once before it is recorded) at learning rate 0: the
+            # parameters come out bitwise as they went in; what it left in phi, the counter, the rings and the status is put back
             step()
-            phi.copy_(phi0)
+            if spring:
+                phi.copy_(phi0)
             st["counter"].fill_(start_epoch + 1)
-            for name in ("ring", "norm_ring", "eff_ring", "status"):
-                st[name].zero_()
-        launch = capture_step(model, step, warm_up, "hipGraph capture of the SPRING step failed") if self.use_graph else step
+            for ring in rings:
+                st[ring].zero_()
+        launch = capture_step(model, step, warm_up, f"hipGraph capture of the {step_name} step failed") if self.use_graph else step
         if callable(lr):   # a schedule: the rate of its epoch in front of every step
             epochs = iter(range(start_epoch + 1, start_epoch + self.num_epochs + 1))
 
@@ -893,14 +865,15 @@ class ModelTrainer:
 
         def status(upto):
             info, skipped = (int(v) for v in st["status"].cpu().tolist())
-            eff = st["eff_ring"].cpu().numpy()
-            for e in range(seen[0] + 1, upto + 1):
-                capped[0] += int(0.0 < eff[e % st["ring_len"]] < float(np.float32(_lr_at(lr, e))))
-            seen[0] = max(seen[0], upto)
-            self.spring_capped_steps, self.spring_skipped_steps = capped[0], skipped
+            if spring:
+                eff = st["eff_ring"].cpu().numpy()
+                for e in range(seen[0] + 1, upto + 1):
+                    capped[0] += int(0.0 < eff[e % st["ring_len"]] < float(np.float32(_lr_at(lr, e))))
+                seen[0] = max(seen[0], upto)
+                self.spring_capped_steps, self.spring_skipped_steps = capped[0], skipped
             if skipped and not warned[0]:
                 warned[0] = True
-                warnings.warn(f"SPRING: {skipped} of the first {upto - start_epoch} steps were skipped (status of the last step: {info}; > 0: that pivot of "
+                warnings.warn(f"{name}: {skipped} of the first {upto - start_epoch} steps were skipped (status of the last step: {info}; > 0: that pivot of "
                               f"the shifted B x B matrix is not positive, -1: the step is not finite) -- more damping")
 
         def fetched(epoch, new):
@@ -910,7 +883,7 @@ class ModelTrainer:
         params = run_device_loop(model, opt_state, run.get_params, replay, loss_ring_reader(model, st, start_epoch + 1, after=status), run.record,
                                  start_epoch + 1, start_epoch + self.num_epochs, self.log_every,
                                  lambda epoch, params: run.checkpoint(int(run.rng.integers(1 << 31)), epoch, params, False), 100, fetched)
-        if run.verbose:
+        if spring and run.verbose:
             print(f"SPRING: the norm constraint bound {capped[0]} and the solver skipped {self.spring_skipped_steps} of {self.num_epochs} steps")
         return params
 
