@@ -33,7 +33,10 @@ MFMA_FLAGS = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-p
 # units that issue MFMA under a file name that says neither "mfma" nor "etile" (the fp64 products of stochastic reconfiguration)
 MFMA_UNITS = {"wf_kernels_sr.hip"}
 # per translation unit: the two-row-block reverse kernels under the max-ilp scheduling strategy (-6 % for them, +1 % for the one-row-block form)
-EXTRA_FLAGS = {"wf_etile_bwd_k2.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+EXTRA_FLAGS = {"wf_etile_bwd_k2.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+               # the two-tile k_mfma (own-walker layout): two waves per SIMD leave the interleaving of the two tiles to the instruction order;
+               # 2^20 He walkers at 8 x 2: 0.243 ms with the default strategy, 0.235 with max-ilp (profiles/mfma_paired_sched_variants.txt)
+               "wf_mfma_inst_d2t2.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
 
 def _hipcc():

@@ -34,6 +34,9 @@ constexpr int64_t kTileSampleMin = 16384;  // wf_sample / wf_inverse_fwd: the st
 // loops) needs 1.4 ms, and stays ahead up to ~2^18 walkers (65536: 1.1 vs 1.9 ms; 2^18: 4.4 vs 4.2-4.6 ms; 2^20: 17.3 vs
 // 15.9-17.3 ms, scratch/sampler_crossover.py): the switch sits at 2^17.
 constexpr int64_t kWaveSampleMax = 131072;
+// k_mfma, headline family: 8 waves x 2 paired tiles (own-walker layout, wf_mfma_impl.h) from here on, 16 waves x 1 tile below.  At 2^16 walkers
+// and fewer the two-tile shape fills half the CUs, and at 2^18 (two pairs per wave) it is still 8 % behind (profiles/mfma_paired_crossover.txt).
+constexpr int64_t kMfmaPairMin = 524288;
 inline int64_t env_energy_tile_min() { return env_i64("WF_ENERGY_TILE_MIN", kEnergyTileMin); }
 inline int64_t env_energy_tile_chunk() { return env_i64("WF_ENERGY_TILE_CHUNK", kEnergyTileChunk); }   // (the caller clamps it to >= 1024)
 inline int64_t env_sample_tile_min() { return env_i64("WF_SAMPLE_TILE_MIN", kTileSampleMin); }

@@ -225,9 +225,12 @@ int waves_per_group(int tiles, int nbk) {
     // (two row blocks per dimension: 0.347 ms at 12 waves, 0.354 at 16, 0.369 at 8 -- scratch/time_waves.py, 33-knot He, 2^20 walkers)
     return (v == 8 || v == 12 || v == 16) ? v : (nbk == 2 ? 12 : 16);
 }
-int tiles_per_wave() {
+// WF_MFMA_TILES as given; with neither knob set the headline family (`paired`: the own-walker two-tile kernel exists for it) takes two tiles
+// per wave, at 8 waves, from kMfmaPairMin walkers on (wf_env.h)
+int tiles_per_wave(int64_t B, bool paired) {
     const int v = env_mfma_tiles();
-    return (v == 1 || v == 2) ? v : 1;
+    if (v == 1 || v == 2) return v;
+    return (paired && env_mfma_waves() == 0 && B >= kMfmaPairMin) ? 2 : 1;
 }
 
 }  // namespace
@@ -283,7 +286,7 @@ int launch_mfma(int D, int nbk, const MfmaDev* mdev, int lds_bytes, int mode, co
     hipStream_t s = (hipStream_t)stream;
 #define GO(DD, KK, WW) return launch_dw<DD, KK, WW, 1>(mdev, lds_bytes, mode, x, B, out, u, idx, s)
     if (D == 2 && nbk == 1) {   // the headline shape: several workgroup shapes are built (tuning / reproducibility test)
-        if (tiles_per_wave() == 2 && !idx) {   // (bin indices: one-tile kernels only)
+        if (!idx && tiles_per_wave(B, mfma::spec_family(mdev, 2)) == 2) {   // (bin indices: one-tile kernels only)
             if (waves_per_group(2, 1) == 4) return launch_dw<2, 1, 4, 2>(mdev, lds_bytes, mode, x, B, out, u, idx, s);
             return launch_dw<2, 1, 8, 2>(mdev, lds_bytes, mode, x, B, out, u, idx, s);
         }

@@ -477,8 +477,124 @@ __device__ __forceinline__ void stage_floats(const float* __restrict__ src, floa
     }
 }
 
+// ---- Two tiles per wave of the headline family (D = 2, NBK = 1, SPEC): the "own-walker" layout.  The MFMA phases hold a tile's walker on
+// lane & 31 with 16 rows per lane half, so a one-tile wave computes everything that depends on the walker alone twice.  A two-tile wave holds
+// 64 walkers on 64 lanes: lane L OWNS walker pair * 64 + L (lanes 0-31 tile 0's, lanes 32-63 tile 1's) and computes that walker's arithmetic
+// once -- box transform, mesh indices, dimension-0 lerps, row sums, rS / rs / y / log dy, the prior's scale, norm and sign, the result.  The
+// two layouts meet at v_permlane32_swap (a, b): the high half of a and the low half of b change places.
+//   own -> tile   swap(own, own) = (tile 0's value on both halves, tile 1's value on both halves)
+//   tile -> own   swap(p0, p1) = (low-half partials, high-half partials) of the lane's own walker; their sum is xhalf_sum's lo + hi
+// The operations on a walker's values, their order and their operands are those of the one-tile kernel: same bits.
+__device__ __forceinline__ void pair_bcast(float own, float (&tl)[2]) {
+    const unsigned u = __float_as_uint(own);
+    const auto s = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    tl[0] = __uint_as_float(s[0]);
+    tl[1] = __uint_as_float(s[1]);
+}
+__device__ __forceinline__ void pair_bcast(int own, int (&tl)[2]) {
+    const auto s = __builtin_amdgcn_permlane32_swap((unsigned)own, (unsigned)own, false, false);
+    tl[0] = (int)s[0];
+    tl[1] = (int)s[1];
+}
+// the B operand of the first layer's 32x32x2 MFMA (x0 on the low half, x1 on the high half) of both tiles in one exchange; in[t][0] = in[t][1]:
+// hidden_layers' choice by lane half picks the same register either way
+__device__ __forceinline__ void pair_operand(float x0, float x1, float (&in)[2][2]) {
+    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(x0), __float_as_uint(x1), false, false);
+    in[0][0] = in[0][1] = __uint_as_float(s[0]);
+    in[1][0] = in[1][1] = __uint_as_float(s[1]);
+}
+__device__ __forceinline__ float pair_sum(float p0, float p1) {
+    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+    return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
+__device__ __forceinline__ float pair_max(float p0, float p1) {
+    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+    return fmaxf(__uint_as_float(s[0]), __uint_as_float(s[1]));
+}
+// what the row work of a tile reads of the owners' Lerp: il and t, ir in the FAR instantiation only
+template <bool FAR>
+__device__ __forceinline__ void pair_lerp(const Lerp& own, Lerp (&tl)[2]) {
+    int il[2], ir[2];
+    float t[2];
+    pair_bcast(own.il, il);
+    pair_bcast(own.t, t);
+    if (FAR) pair_bcast(own.ir, ir);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        tl[k].il = il[k];
+        tl[k].ir = FAR ? ir[k] : il[k];
+        tl[k].xl = tl[k].xr = 0;
+        tl[k].t = t[k];
+    }
+}
+// rows_lerp_dot of one tile (one row block) up to the sum over the lane halves
+template <int NO, bool FAR>
+__device__ __forceinline__ void rows_lerp_part(const f32x16& v, const float* __restrict__ tab, const Lerp& Lt, int h, const float* bnd, float (&part)[NO]) {
+#pragma unroll
+    for (int o = 0; o < NO; ++o) part[o] = 0.0f;
+    f32x16 A[NO], Bv[NO];
+    fetch_block<1, NO, FAR>(A, Bv, tab, Lt, h, bnd, 0);
+    block_dot<NO>(v, A, Bv, Lt.t, part);
+}
+// ispline_eval of a pair: the weights v[t] and the records in tile layout, everything else in the owners'
+template <bool FAR>
+__device__ __forceinline__ void pair_ispline(const f32x16 (&v)[2], const float* __restrict__ tab, const float* __restrict__ rsum, const Lerp& Lp, int h,
+                                             const float* bnd, float rS, float rs, float& y, float& logdy) {
+    Lerp Lt[2];
+    pair_lerp<FAR>(Lp, Lt);
+    float part[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) rows_lerp_part<2, FAR>(v[t], tab, Lt[t], h, bnd, part[t]);
+    const f32x4 c = load4(rsum + (size_t)Lp.il * 4);   // the row sums of rows_lerp_dot, once per walker
+    f32x4 r = c;
+    bool far = false;
+    if (FAR) {
+        far = Lp.ir != Lp.il && Lp.ir != Lp.il + 1;
+        r = load4(rsum + (size_t)Lp.ir * 4);
+    }
+    float num[2], rl[2], rr[2];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        rl[o] = c[o];
+        rr[o] = far ? r[o] : c[2 + o];
+        num[o] = pair_sum(part[0][o], part[1][o]);
+    }
+    const float ynum = __builtin_fmaf(rs, __builtin_fmaf(rr[0] - rl[0], Lp.t, rl[0]), num[0]);
+    const float dnum = __builtin_fmaf(rs, __builtin_fmaf(rr[1] - rl[1], Lp.t, rl[1]), num[1]);
+    y = ynum * rS;
+    logdy = fast_log(__builtin_fmaf(dnum, rS, 1e-7f));
+}
+// rows_dot of a pair (the prior's one-order table), summed into the owners' layout
+template <bool FAR>
+__device__ __forceinline__ float pair_rows_dot(const f32x16 (&c)[2], const float* __restrict__ tab, const Lerp& Lp, int h, const float* bnd) {
+    Lerp Lt[2];
+    pair_lerp<FAR>(Lp, Lt);
+    float part[2][1];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) rows_lerp_part<1, FAR>(c[t], tab, Lt[t], h, bnd, part[t]);
+    return pair_sum(part[0][0], part[1][0]);
+}
+// sigmoid_block of one tile (one row block, no gate) up to the sums over the lane halves
+__device__ __forceinline__ void sigmoid_part(f32x16& o, const float* fk_lds, int h, float& s1, float& sf) {
+    const f32x16 fk = load16(fk_lds + h * 16);
+    s1 = sf = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float v = act_sigmoid(o[r]);
+        o[r] = v;
+        s1 += v;
+        sf = __builtin_fmaf(v, fk[r], sf);
+    }
+}
+// the models of the specialised (SPEC) instantiations
+inline bool spec_family(const MfmaDev* m, int D) {
+    return m->box_kind == WF_BOX_MEAN && m->layer_kind == WF_LAYER_IMADE && m->prior_kind == WF_PRIOR_WAVEFLOW && (D > 2 || !m->staged) && !m->exact_div &&
+           !m->i_gate && !m->p_gate && !m->p_bias;
+}
+
 // One wave = T tiles of 32 walkers (T = 2: two independent dependency chains per wave, so that one tile's activation / spline
 // VALU work sits in the other tile's MFMA shadow inside the same instruction stream; the A operands are read from LDS once per pair).
+// The two-tile SPEC kernel of D = 2, NBK = 1 runs in the own-walker layout above.
 // IDX: the bin-index output (a diagnostic) is compiled into its own instantiation: the per-lane pointer tests would otherwise
 // cut the hot loop into a hundred basic blocks that the instruction scheduler cannot move work across.
 // SPEC: the headline family (mean-type box, IMADE layers, Waveflow prior, every net resident in LDS, division-free x_l / n) with the
@@ -893,7 +1009,159 @@ __global__ __launch_bounds__(kWaves * 64) void k_mfma(const MfmaDev mm, int mode
             }
     };
 
-    if (!staged) {
+    if constexpr (SPEC && D == 2 && NBK == 1 && T == 2 && !IDX) {
+        // ---- the pair pass in the own-walker layout (pair_bcast ... sigmoid_part above): lane L owns walker pair * 64 + L.  `c0, c1, logdet`
+        // and every scalar below are the owner's; f32x16 values, Frag and `in` are in tile layout.
+        const f32x4* comp_p = mm.comp2 + (size_t)mm.n_layers * mm.n_mesh;
+        for (;;) {
+            int q = 0;
+            if (lane == 0) q = __hip_atomic_fetch_add(&next_slot, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            q = __builtin_amdgcn_readfirstlane(q);
+            if (q >= my_slots) break;
+            const int64_t chunk = (int64_t)blockIdx.x + (int64_t)(q / kWaves) * gridDim.x;
+            const int64_t wo = (chunk * kWaves + q % kWaves) * 64 + lane;   // tiles 2 * pair and 2 * pair + 1; may lie behind the batch: computed, never stored
+            const bool valid = wo < B;
+            const int64_t wl = valid ? wo : B - 1;
+            float c0 = xg[wl * 2], c1 = xg[wl * 2 + 1], logdet;
+            if (presort) {
+                const float a = c0, b = c1;
+                const bool sw = a > b;
+                c0 = sw ? b : a;
+                c1 = sw ? a : b;
+            }
+            {   // BoxTransformLayer, mean type (load_box)
+                float s = 0.0f;
+                s = s + c0;
+                s = s + c1;
+                const float mean = s / (float)D;
+                const float l = mean - c0;
+                const float wd = c1 - c0;
+                const float diff = c1 - c0;
+                const float n0 = diff / box_space0;
+                const float n1 = (mean + L - l) / (2 * L - wd + tol);
+                logdet = box_nlog0 - fast_log(2 * L - wd + tol);
+                c0 = n0;
+                c1 = n1;
+            }
+            float in[2][2];
+            Frag h2[2][2];
+            f32x16 pend[2];
+            for (int l = 0; l < mm.n_layers; ++l) {
+                const float* net = slots + (size_t)l * mm.net_floats;
+                pair_operand(c0, c1, in);
+                hidden_layers<2, 1, 2>(net, in, lane, h2, pend);
+                const Lerp L0 = make_lerp(c0, mm.n_mesh, rn_mesh, 0);
+                const f32x2 d0 = comp_lerp(mm.comp2 + (size_t)l * mm.n_mesh, L0);
+                logdet = logdet + fast_log(d0[1] + 1e-7f);
+                f32x16 v[2];
+                out_block_first<2, 1, 2>(net, h2, pend, lane, v);
+                float s1p[2], sfp[2];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) sigmoid_part(v[t], fkI, h, s1p[t], sfp[t]);
+                const float S1 = pair_sum(s1p[0], s1p[1]), Sf = pair_sum(sfp[0], sfp[1]);
+                const float rs = mm.i_reg * S1;
+                const float rS = __builtin_amdgcn_rcpf(__builtin_fmaf(rs, mm.F_I, Sf));
+                const Lerp L1 = make_lerp(c1, mm.n_mesh, rn_mesh, 0);
+                float y, ld;
+                if (!any_far(L1)) pair_ispline<false>(v, mm.tabI, mm.rsI, L1, h, bndI, rS, rs, y, ld);
+                else pair_ispline<true>(v, mm.tabI, mm.rsI, L1, h, bndI, rS, rs, y, ld);
+                logdet = logdet + ld;
+                c0 = y;        // Reverse (bijections.py:337-340)
+                c1 = d0[0];
+            }
+            float result = logdet;
+            if (mode != 2) {   // ---- density head (Waveflow prior)
+                const float* net = slots + (size_t)mm.n_layers * mm.net_floats;
+                pair_operand(c0, c1, in);   // the conditioner sees the unclipped u (wavefunctions.py:40)
+                hidden_layers<2, 1, 2>(net, in, lane, h2, pend);
+                float lp = 0.0f, prod = 1.0f;
+                auto factor = [&](int d, float val) __attribute__((always_inline)) {
+                    const bool constrained = (mm.constrained_mask >> d) & 1u;
+                    if (mode == 0) {
+                        float pr = val * val;
+                        if (constrained) pr = pr * 0.5f;
+                        lp = lp + fast_log(pr + 1e-7f);
+                    } else {
+                        const float vv = constrained ? val * 0.70710678118654752f : val;
+                        prod = prod * vv;
+                    }
+                };
+                const float u0 = fminf(fmaxf(c0, 0.0f), 1.0f), u1 = fminf(fmaxf(c1, 0.0f), 1.0f);   // the spline sees the clipped one (:45)
+                const Lerp P0 = make_lerp(u0, mm.n_mesh, rn_mesh, 0);
+                factor(0, comp_lerp(comp_p, P0)[0]);
+                const Lerp P1 = make_lerp(u1, mm.n_mesh, rn_mesh, 0);
+                f32x16 o[2];
+                out_block_first<2, 1, 2>(net, h2, pend, lane, o);
+                float s1p[2], amp[2];
+                {
+                    const f32x16 keep = load16(fkP + h * 16);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        float s1 = 0.0f, amax = 0.0f;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            s1 += o[t][r];
+                            o[t][r] = o[t][r] * keep[r];
+                            amax = fmaxf(amax, fabsf(o[t][r]));
+                        }
+                        s1p[t] = s1;
+                        amp[t] = amax;
+                    }
+                }
+                // the power-of-two scale of the walker's 32 values (see the one-tile body below), formed once per walker and handed to both halves
+                const float s1 = pair_sum(s1p[0], s1p[1]), amax = pair_max(amp[0], amp[1]);
+                const int ex = amax > 0.0f ? __builtin_amdgcn_frexp_expf(amax) : 0;
+                const float scale = mm.prior_quotient ? 1.0f / s1 : __builtin_amdgcn_ldexpf(1.0f, -ex);
+                float sc[2], n2p[2];
+                pair_bcast(scale, sc);
+                f32x16 c[2];
+                const _Float16* obh = reinterpret_cast<const _Float16*>(ob2b);
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    Frag of;
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        float r8[8];
+#pragma unroll
+                        for (int jj = 0; jj < 8; ++jj) r8[jj] = o[t][8 * s + jj] * sc[t];
+                        split8(r8, of.hi[s], of.lo[s]);
+                    }
+                    c[t] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const f16x8 ah = *reinterpret_cast<const f16x8*>(obh + (s * 64 + lane) * 8);
+                        const f16x8 al = *reinterpret_cast<const f16x8*>(obh + 1024 + (s * 64 + lane) * 8);
+                        c[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, of.hi[s], c[t], 0, 0, 0);
+                        c[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, of.lo[s], c[t], 0, 0, 0);
+                        c[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, of.hi[s], c[t], 0, 0, 0);
+                    }
+                    float n2 = 0.0f;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) n2 = __builtin_fmaf(c[t][r], c[t][r], n2);
+                    n2p[t] = n2;
+                }
+                const float rnorm = __builtin_amdgcn_rsqf(pair_sum(n2p[0], n2p[1]));
+                const float dot = !any_far(P1) ? pair_rows_dot<false>(c, mm.tabP, P1, h, bndP) : pair_rows_dot<true>(c, mm.tabP, P1, h, bndP);
+                const float v0 = dot * rnorm;
+                factor(1, (s1 < 0.0f && !mm.prior_quotient) ? -v0 : v0);
+                result = mode != 0 ? prod * __expf(0.5f * logdet) : lp + logdet;
+                c0 = u0;
+                c1 = u1;
+            }
+            if (valid) {   // every lane stores its own walker: 64 consecutive results per wave
+                if (f16_bad) result = __builtin_nanf("");   // a packed weight outside the fp16 range (k_fold_bias)
+                if (presort && mode == 1) {   // (-1)^inversions of the walker as it arrived: the row is read again
+                    const float xr0 = xg[wo * 2], xr1 = xg[wo * 2 + 1];
+                    if (xr0 > xr1) result = -result;
+                }
+                out[wo] = result;
+                if (u_out) {
+                    u_out[wo * 2] = c0;
+                    u_out[wo * 2 + 1] = c1;
+                }
+            }
+        }
+    } else if (!staged) {
         for (;;) {
             int q = 0;
             if (lane == 0) q = __hip_atomic_fetch_add(&next_slot, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -991,8 +1259,7 @@ int launch_dw(const MfmaDev* mdev, int lds_bytes, int mode, const float* x, int6
         else return WF_ERR_UNSUPPORTED;
     }
     if constexpr (D == 2 || (D == 8 && NBK == 1)) {   // the specialised build exists for the two-particle shapes and for the 8-electron chain (config C4)
-        if (mdev->box_kind == WF_BOX_MEAN && mdev->layer_kind == WF_LAYER_IMADE && mdev->prior_kind == WF_PRIOR_WAVEFLOW && (D > 2 || !mdev->staged) &&
-            !mdev->exact_div && !mdev->i_gate && !mdev->p_gate && !mdev->p_bias)
+        if (spec_family(mdev, D))
             return launch_dwi<D, NBK, kWaves, T, false, true>(mdev, lds_bytes, mode, x, B, out, u, nullptr, s);
     }
     return launch_dwi<D, NBK, kWaves, T, false, false>(mdev, lds_bytes, mode, x, B, out, u, nullptr, s);
