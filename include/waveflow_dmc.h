@@ -38,8 +38,7 @@
  * and w_b = 0 for a walker whose old x, psi, grad or e_loc is not finite.  E_T is *e_trial_dev.
  * The generation record (fp64[6]): sum w, sum w e_new, sum w e_new^2, moves accepted, moves rejected for leaving the domain (flag != 0 or
  * psi' psi <= 0), moves rejected because a new value is not finite (flag == 0, psi' psi > 0 or NaN).  Walkers of weight 0 add nothing to the
- * first three.  The sums are formed in an order that depends on B alone -- the order of k_observe / k_observe_reduce: lane sums in walker
- * order over the grid of wf_observe_accumulate, a fixed shuffle tree per wave, waves in order, blocks in order, one thread adds.  No
+ * first three.  The sums are formed in the order that waveflow_observe.h states ("Reproducibility"), which depends on B alone.  No
  * floating-point atomics.
  *
  * RECONFIGURE: the comb, in integers -- exact, and independent of any summation order.

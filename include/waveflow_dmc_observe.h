@@ -36,11 +36,10 @@
  *                for its ancestor.  Per configuration: V_en and V_ee by the fp32 rule of waveflow_observe.h (the same bits), the density and
  *                pair bins by its bin rule (scale = (float)n_bins / (hi - lo) in fp32 on the host, t = (x_d - lo) * scale and
  *                t = fabsf(x_i - x_j) * scale_pair, bin (int)t where 0 <= t < n_bins, otherwise counts[2] or counts[3]); a configuration with
- *                a coordinate that is not finite adds 1 to counts[1] and nothing else.  The fp64 sums of one lag are formed in the order of
- *                waveflow_observe.h, which depends on B alone: lane sums in k order over the grid of wf_observe_accumulate, a fixed shuffle tree
- *                per wave, waves in order, block partials in block order, one thread adds them to sums.  No floating-point atomics;
- *                histograms and counters are integers.  Distinct ancestors of a served slot: the number of different values in anc[s], an
- *                integer; B for lag 0.  Then the series row is written and measurements += 1.
+ *                a coordinate that is not finite adds 1 to counts[1] and nothing else.  The fp64 sums of one lag are formed over k in the
+ *                order that waveflow_observe.h states ("Reproducibility"), which depends on B alone.  No floating-point atomics; histograms
+ *                and counters are integers.  Distinct ancestors of a served slot: the number of different values in anc[s], an integer; B
+ *                for lag 0.  Then the series row is written and measurements += 1.
  *   3. RETAG     only when measuring, slot s* = (g / stride) mod n_slots:  snap[s*] <- x, anc[s*][k] <- k, tag[s*] <- g.  In a run that calls
  *                the update once per generation, s* is the slot that has just been measured at lag n_slots, if it was not empty.
  * Every kernel is launched in every call and decides from g on the device, so the sequence can be captured in a hipGraph with stride > 1.

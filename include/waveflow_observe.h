@@ -20,10 +20,13 @@
  *     t >= 0 && t < n_bins: bin (int)t (density: row d) + 1; otherwise counts[2] (density) or counts[3] (pair) + 1.
  * (fp32 rounding puts nextafterf(hi, lo) at t == n_bins, outside: that is the rule.)
  *
- * Reproducibility: the fp64 sums of one call are formed in an order that depends on B alone -- lane sums in walker order, a fixed shuffle
- * tree per wave, waves in order per block, block partials in block order -- and are added to sums_dev by one thread.  No floating-point
- * atomics.  Two calls on the halves of a batch into one accumulator leave the bits of two calls into two accumulators whose sums are then
- * added.  Histograms and counters are integers: their order does not matter.
+ * Reproducibility: the fp64 sums of one call are formed in an order that depends on B alone -- lane sums in walker order over a grid-stride
+ * loop (256 lanes per block, min(ceil(B / 256), 1024) blocks), a fixed shuffle tree per wave (offsets 32, 16, .. 1), the four waves of a block
+ * in order, block partials in block order from 0 -- and are added to sums_dev by one thread.  This is the one order of every fp64 sum behind
+ * waveflow_overlap.h, waveflow_dmc.h and waveflow_dmc_observe.h as well; waveflow_amd/csrc/wf_accum.h states it step by step and
+ * waveflow_amd/_accum.py (ordered_sum) restates it in numpy.  No floating-point atomics.  Two calls on the halves of a batch into one
+ * accumulator leave the bits of two calls into two accumulators whose sums are then added.  Histograms and counters are integers: their
+ * order does not matter.
  *
  * The accumulators are caller-owned and caller-zeroed; calls add to them.  None of the entries synchronises with the host.
  */

@@ -15,10 +15,9 @@
  * to counts[0] and (double)r_k, (double)r_k * (double)r_k to sums[k][0], sums[k][1].  ratios[k][b] (optional) receives r_k of every walker
  * as computed, skipped walkers included.
  *
- * Reproducibility: the fp64 sums of one call are formed in an order that depends on B alone -- lane sums in walker order over the grid-stride
- * loop (256 lanes per block, min(ceil(B / 256), 1024) blocks), a fixed shuffle tree per wave (offsets 32, 16, .. 1), the four waves of a block
- * in order, block partials in block order -- and are added to sums_dev by one thread.  No floating-point atomics.  Two calls on the halves of
- * a batch into one accumulator leave the bits of two calls into two accumulators whose sums are then added.
+ * Reproducibility: the fp64 sums of one call are formed in the order that waveflow_observe.h states ("Reproducibility"), which depends on B
+ * alone, and are added to sums_dev by one thread.  No floating-point atomics.  Two calls on the halves of a batch into one accumulator leave
+ * the bits of two calls into two accumulators whose sums are then added.
  *
  * The penalty method L = E[psi] + sum_k lambda_k S_k^2 has the gradient 2 E[(e~ - mean e~) O] with
  *     e~_b = e_b + sum_k lambda_k a_k (r_kb - a_k),     a_k = sums[k][0] / counts[0]

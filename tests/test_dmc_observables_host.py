@@ -11,50 +11,18 @@ import numpy as np
 import pytest
 
 from waveflow_amd import _lib, core, dmc, dmc_observables as fwo, observables as obs, sr
+from abi_header import c_class, ctypes_class, header_prototypes, no_comments
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "waveflow_dmc_observe.h")
-SCALAR = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "f32", "double": "f64"}
 NAMES = ["wf_dmc_fw_workspace_bytes", "wf_dmc_fw_update", "wf_vqmc_dmc_fw_workspace_bytes", "wf_vqmc_dmc_fw_step"]
 PROTONS = [-0.7, 0.4]
-
-
-def _no_comments():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _c_class(text, is_return=False):
-    words = [w for w in text.replace("*", " * ").split() if w != "const"]
-    if "*" in words:
-        return "string" if is_return and words[0] == "char" else "pointer"
-    if is_return and words == ["void"]:
-        return "void"
-    return SCALAR[words[0]]   # KeyError: a type this test does not know
-
-
-def _header_prototypes():
-    """name -> (class of the return type, [class per argument]) for every wf_* function the header declares, in its order."""
-    out = {}
-    for ret, name, args in re.findall(r"^([\w \*]+?)\b(wf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _no_comments(), flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        assert name not in out, name
-        out[name] = (_c_class(ret, True), [] if args == ["void"] else [_c_class(a.rsplit(None, 1)[0] if "*" not in a else a) for a in args])
-    return out
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
-        return "pointer"
-    return {ctypes.c_void_p: "pointer", ctypes.c_char_p: "string", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64",
-            ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
 
 
 def test_prototype_table_matches_the_header_and_the_library():
     """dmc_observables.PROTOTYPES against the header: the same functions in the same order, per position the same argument class; every symbol
     exported; lib() applies the table; nothing of it is in an existing table, and those keep their sizes; ABI version 2."""
-    declared = _header_prototypes()
+    declared = header_prototypes(HEADER)
     assert list(declared) == list(fwo.PROTOTYPES) == NAMES
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
@@ -64,8 +32,8 @@ def test_prototype_table_matches_the_header_and_the_library():
     for name, (ret, args) in declared.items():
         restype, argtypes = fwo.PROTOTYPES[name]
         assert len(argtypes) == len(args), (name, len(argtypes), len(args))
-        assert [_ctypes_class(t) for t in argtypes] == args, (name, args)
-        assert _ctypes_class(restype) == ret, (name, ret)
+        assert [ctypes_class(t) for t in argtypes] == args, (name, args)
+        assert ctypes_class(restype) == ret, (name, ret)
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == list(argtypes), name
     assert fwo.PROTOTYPES["wf_dmc_fw_update"][1][6] is ctypes.POINTER(fwo.DmcFw)
@@ -76,7 +44,7 @@ def test_prototype_table_matches_the_header_and_the_library():
         assert not set(declared) & set(table)
     assert len(_lib.PROTOTYPES) == 55 and len(obs.PROTOTYPES) == 4 and len(dmc.PROTOTYPES) == 8
     hdr = open(HEADER).read()
-    assert '#include "waveflow_dmc.h"' in hdr and "WF_ABI_VERSION" not in _no_comments()
+    assert '#include "waveflow_dmc.h"' in hdr and "WF_ABI_VERSION" not in no_comments(HEADER)
     for name, value in (("WF_DMC_FW_MAX_SLOTS", fwo.MAX_SLOTS), ("WF_DMC_FW_COUNTS", len(fwo.COUNTS)), ("WF_DMC_FW_SERIES", len(fwo.SERIES))):
         assert re.search(rf"#define\s+{name}\s+{value}\b", hdr), name
     assert re.search(r"#define\s+WF_DMC_FW_EMPTY\s+0x(F{16})ull", hdr) and fwo.EMPTY == 0xFFFFFFFFFFFFFFFF
@@ -85,20 +53,20 @@ def test_prototype_table_matches_the_header_and_the_library():
 
 def test_tracker_struct_matches_the_header():
     """wf_dmc_fw field by field: nine pointers, then eight 4-byte fields -- names, order, kinds, offsets and size of dmc_observables.DmcFw."""
-    body = re.search(r"typedef\s+struct\s+wf_dmc_fw\s*\{(.*?)\}\s*wf_dmc_fw\s*;", _no_comments(), flags=re.S).group(1)
+    body = re.search(r"typedef\s+struct\s+wf_dmc_fw\s*\{(.*?)\}\s*wf_dmc_fw\s*;", no_comments(HEADER), flags=re.S).group(1)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
         if decl:
             kind, names = decl.replace("*", " * ").split(None, 1) if "*" not in decl else decl.replace("*", " * ").rsplit(None, 1)
             for name in names.split(","):                                   # (float lo, hi;)
-                fields.append((name.strip(), _c_class(kind)))
+                fields.append((name.strip(), c_class(kind)))
     want = [(n, "pointer") for n in ("snap_dev", "anc_dev", "tag_dev", "counts_dev", "density_dev", "pair_dev", "sums_dev", "measurements_dev",
                                      "series_dev")]
     want += [("n_slots", "i32"), ("stride", "i32"), ("series_len", "i32"), ("n_density_bins", "i32"), ("n_pair_bins", "i32"), ("lo", "f32"),
              ("hi", "f32"), ("reserved", "i32")]
     assert fields == want
-    assert [(n, _ctypes_class(t)) for n, t in fwo.DmcFw._fields_] == want
+    assert [(n, ctypes_class(t)) for n, t in fwo.DmcFw._fields_] == want
     assert [getattr(fwo.DmcFw, n).offset for n, _ in want] == [8 * i for i in range(9)] + [72 + 4 * i for i in range(8)]
     assert ctypes.sizeof(fwo.DmcFw) == 104
 

@@ -255,6 +255,29 @@ def test_acceptance_against_fp64_numpy(B, D, limit):
         assert np.array_equal(_bits(a), _bits(b))
 
 
+# one lane, across a wave, across a block, 258 blocks (the reduce stages its rows twice), one walker beyond 1024 x 256 (the grid-stride loop
+# runs twice): the smallest sizes at which each stage of the order of summation can go wrong
+ORDER_BS = [1, 65, 257, 65793, 262145]
+
+
+@pytest.mark.parametrize("D", [2, 3])
+@pytest.mark.parametrize("B", ORDER_BS)
+def test_record_sums_are_the_ordered_sum_of_the_device_terms(B, D):
+    """record[0 .. 2] equal, bit for bit, the sums of w, w e and (w e) e in the one order of the device's fp64 sums (_accum.ordered_sum), the
+    terms formed in fp64 from the device's own weights, decisions and local energies; a walker of weight 0 (not finite) enters as 0."""
+    from waveflow_amd._accum import ordered_sum
+    c = _accept_case(B, D, False)
+    state, (w, record, _, _, acc) = _run_accept(c)
+    w, record, acc = w.cpu().numpy(), record.cpu().numpy(), acc.cpu().numpy().astype(bool)
+    e = np.where(acc, state[3].cpu().numpy(), c["e_loc"]).astype(np.float64)
+    live = w != 0
+    assert B < 65 or (~live).any()
+    with np.errstate(all="ignore"):
+        terms = [np.where(live, w, 0.0), np.where(live, w * e, 0.0), np.where(live, (w * e) * e, 0.0)]
+    for k in range(3):
+        assert np.isfinite(record[k]) and record[k].tobytes() == ordered_sum(terms[k]).tobytes(), (k, record[k], ordered_sum(terms[k]))
+
+
 def test_sign_flag_and_not_finite_each_reject_and_are_counted():
     """Proposals that would all be accepted (zero drift on both sides and psi' = psi: logA == 0, A == 1 > u), but for walker 3 (psi' of the
     other sign), walker 5 (flagged) and walker 7 (a Hessian diagonal that is not finite)."""

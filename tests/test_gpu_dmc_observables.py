@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import sorted_walkers
-from test_gpu_dmc import SEED, TAU, BOX, _bits, _capture, _dev, _guide, _he, _three, _waveflow, _a256
+from test_gpu_dmc import ORDER_BS, SEED, TAU, BOX, _bits, _capture, _dev, _guide, _he, _three, _waveflow, _a256
 
 pytestmark = pytest.mark.gpu
 
@@ -114,6 +114,34 @@ def test_update_equals_the_integer_reference(B, D, S, stride):
     again = _drive(B, D, S, stride, check=False)
     for a, b in zip(first, again):
         assert np.array_equal(a, b)                                               # bitwise the same a second time, the fp64 sums included
+
+
+@pytest.mark.parametrize("B", ORDER_BS)
+def test_lag_0_sums_are_the_ordered_sum_of_the_potentials(B):
+    """After one update at generation 0 the sums of lag 0 equal, bit for bit, the sums of V_en, V_en^2, V_ee and V_ee^2 in the one order of
+    the device's fp64 sums (_accum.ordered_sum) over the per-walker potentials of wf_observe_accumulate (psi = 1, no derivatives: the same
+    local_values); a walker that is not finite enters as 0."""
+    import torch
+    from waveflow_amd import dmc_observables as fwo
+    from waveflow_amd import observables as obs
+    from waveflow_amd._accum import ordered_sum
+    D = 2
+    x = sorted_walkers(B, D, 7.0, B + 3)
+    x[3::7, 1] = np.nan
+    x[5::11, 0] = np.inf
+    fin = np.isfinite(x).all(axis=1)
+    fw = fwo.ForwardWalk(B, D, 1, 1, 37, 53, -6.0, 6.0, 2, device="cuda")
+    xd = torch.as_tensor(x).cuda()
+    fwo.update(xd, None, PROTONS, fw, 0)
+    zero = torch.zeros_like(xd)
+    v = obs.accumulate(xd, torch.ones(B, device="cuda"), zero, zero, PROTONS, return_values=True).cpu().numpy().astype(np.float64)
+    sums, counts = fw.sums.cpu().numpy()[0].reshape(-1), fw.counts.cpu().numpy()[0]
+    assert list(counts[:2]) == [fin.sum(), (~fin).sum()] and (B < 65 or not fin.all())
+    with np.errstate(all="ignore"):
+        terms = [v[:, 3], v[:, 3] * v[:, 3], v[:, 4], v[:, 4] * v[:, 4]]
+    for k in range(4):
+        want = ordered_sum(np.where(fin, terms[k], 0.0))
+        assert np.isfinite(sums[k]) and sums[k].tobytes() == want.tobytes(), (k, sums[k], want)
 
 
 def test_update_at_2_pow_20_walkers():

@@ -86,31 +86,6 @@ def _hist_reference(x, nd, npair, lo=LO, hi=HI):
     return density, pair, out_d, out_p
 
 
-def _ordered_sum(v):
-    """The fp64 sum of v [B] in the order of the device (include/waveflow_observe.h): lane sums in walker order over the grid-stride loop, the
-    shuffle tree of a wave, the four waves of a block in order, the blocks in order, then 0 + total.  A skipped walker enters as 0."""
-    B = v.shape[0]
-    blocks = min(-(-B // BLOCK), GRID_BLOCKS)
-    stride = blocks * BLOCK
-    passes = -(-B // stride)
-    padded = np.zeros(passes * stride, f64)
-    padded[:B] = v
-    lanes = np.zeros(stride, f64)
-    for p in range(passes):
-        lanes = lanes + padded[p * stride:(p + 1) * stride]
-    w = lanes.reshape(blocks, BLOCK // 64, 64)
-    for half in (32, 16, 8, 4, 2, 1):
-        w = w[..., :half] + w[..., half:2 * half]
-    w = w[..., 0]
-    per_block = w[:, 0]
-    for k in range(1, BLOCK // 64):
-        per_block = per_block + w[:, k]
-    total = per_block[0]
-    for b in range(1, blocks):
-        total = total + per_block[b]
-    return f64(0.0) + total
-
-
 def _dev(*arrays):
     import torch
     return [torch.as_tensor(a).cuda() for a in arrays]
@@ -157,6 +132,7 @@ def test_per_walker_values_against_fp64(case):
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "B{}-D{}-p{}-bins{}x{}".format(*c))
 def test_sums_against_numpy_of_the_device_values(case):
+    from waveflow_amd._accum import ordered_sum   # the device's order of summation, restated in numpy
     B = case[0]
     _, values, tot = _run(case)
     v = values.astype(f64)
@@ -167,7 +143,7 @@ def test_sums_against_numpy_of_the_device_values(case):
             diff = abs(tot.sums[k, col] - terms.sum())
             worst = max(worst, diff / bound if bound > 0 else (0.0 if diff == 0 else np.inf))
             assert diff <= bound, (k, col, diff, bound)
-            assert tot.sums[k, col] == _ordered_sum(terms), (k, col)       # and bit for bit the documented order
+            assert tot.sums[k, col] == ordered_sum(terms), (k, col)       # and bit for bit the documented order
     print(f"[observables sums, B {B}] worst |device - numpy| / (B 2^-52 sum |v|) {worst:.3e}")
     assert tot.counts[0] == B and tot.counts[1] == 0
 
@@ -229,6 +205,7 @@ def test_edge_walkers_are_counted_outside_and_enter_no_bin(lo, hi, nb):
 
 def test_skipped_walkers_are_counted_and_add_nothing():
     from waveflow_amd import observables as obs
+    from waveflow_amd._accum import ordered_sum
     B, D, nd, npair = 600, 3, 64, 128
     x, psi, grad, hdiag = _inputs(B, D, 21)
     plant = {63: "x", 64: "psi", 255: "grad", 256: "hdiag", 300: "inv"}     # both sides of a wave edge and of a block edge, and one more
@@ -262,7 +239,7 @@ def test_skipped_walkers_are_counted_and_add_nothing():
     v = np.where(keep[:, None], values.astype(f64), 0.0)
     for k in range(5):
         for c, terms in ((0, v[:, k]), (1, v[:, k] * v[:, k])):
-            assert tot.sums[k, c] == _ordered_sum(terms), (k, c)
+            assert tot.sums[k, c] == ordered_sum(terms), (k, c)
             assert abs(tot.sums[k, c] - clean.sums[k, c]) <= B * 2.0 ** -52 * np.abs(terms).sum(), (k, c)
 
 

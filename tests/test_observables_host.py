@@ -11,49 +11,17 @@ import numpy as np
 import pytest
 
 from waveflow_amd import _lib, core, observables as obs, sr
+from abi_header import c_class, ctypes_class, header_prototypes, no_comments
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "waveflow_observe.h")
-SCALAR = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "f32", "double": "f64"}
 NAMES = ["wf_observe_workspace_bytes", "wf_observe_accumulate", "wf_vqmc_observe_step_workspace_bytes", "wf_vqmc_observe_step"]
-
-
-def _no_comments():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _c_class(text, is_return=False):
-    words = [w for w in text.replace("*", " * ").split() if w != "const"]
-    if "*" in words:
-        return "string" if is_return and words[0] == "char" else "pointer"
-    if is_return and words == ["void"]:
-        return "void"
-    return SCALAR[words[0]]   # KeyError: a type this test does not know
-
-
-def _header_prototypes():
-    """name -> (class of the return type, [class per argument]) for every wf_* function the header declares, in its order."""
-    out = {}
-    for ret, name, args in re.findall(r"^([\w \*]+?)\b(wf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _no_comments(), flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        assert name not in out, name
-        out[name] = (_c_class(ret, True), [] if args == ["void"] else [_c_class(a.rsplit(None, 1)[0] if "*" not in a else a) for a in args])
-    return out
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
-        return "pointer"
-    return {ctypes.c_void_p: "pointer", ctypes.c_char_p: "string", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64",
-            ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
 
 
 def test_prototype_table_matches_the_header_and_the_library():
     """observables.PROTOTYPES against include/waveflow_observe.h: the same functions in the same order, per position the same argument class;
     every symbol exported; observables.lib() applies the table; nothing of it is in the existing tables, which keep their sizes; ABI version 2."""
-    declared = _header_prototypes()
+    declared = header_prototypes(HEADER)
     assert list(declared) == list(obs.PROTOTYPES) == NAMES
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
@@ -63,8 +31,8 @@ def test_prototype_table_matches_the_header_and_the_library():
     for name, (ret, args) in declared.items():
         restype, argtypes = obs.PROTOTYPES[name]
         assert len(argtypes) == len(args), (name, len(argtypes), len(args))
-        assert [_ctypes_class(t) for t in argtypes] == args, (name, args)
-        assert _ctypes_class(restype) == ret, (name, ret)
+        assert [ctypes_class(t) for t in argtypes] == args, (name, args)
+        assert ctypes_class(restype) == ret, (name, ret)
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == list(argtypes), name
     assert declared["wf_vqmc_observe_step"][1][3] == "u64" and declared["wf_observe_accumulate"][1][4] == "i64"
@@ -74,7 +42,7 @@ def test_prototype_table_matches_the_header_and_the_library():
         assert not set(declared) & set(table)
     assert len(_lib.PROTOTYPES) == 55 and len(sr.PROTOTYPES) == 4 and len(sr.STEP_PROTOTYPES) == 2 and len(sr.SPRING_PROTOTYPES) == 5
     hdr = open(HEADER).read()
-    assert '#include "waveflow_hip.h"' in hdr and "WF_ABI_VERSION" not in _no_comments()
+    assert '#include "waveflow_hip.h"' in hdr and "WF_ABI_VERSION" not in no_comments(HEADER)
     assert re.search(r"#define\s+WF_OBSERVE_SCALARS\s+5\b", hdr) and len(obs.SCALARS) == 5
     assert obs.SCALARS == ("e_loc", "t_lap", "t_grad", "v_en", "v_ee")
     assert L.wf_abi_version() == 2
@@ -82,17 +50,17 @@ def test_prototype_table_matches_the_header_and_the_library():
 
 def test_accumulator_struct_matches_the_header():
     """wf_observe_acc field by field: four pointers, two int32, two floats -- names, order, kinds, offsets and size of observables.ObserveAcc."""
-    body = re.search(r"typedef\s+struct\s+wf_observe_acc\s*\{(.*?)\}\s*wf_observe_acc\s*;", _no_comments(), flags=re.S).group(1)
+    body = re.search(r"typedef\s+struct\s+wf_observe_acc\s*\{(.*?)\}\s*wf_observe_acc\s*;", no_comments(HEADER), flags=re.S).group(1)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
         if decl:
             first, *more = [n.strip() for n in decl.split(",")]    # "float lo, hi": one kind, several names
             kind, name = first.replace("*", " * ").rsplit(None, 1)
-            fields += [(n, _c_class(kind)) for n in [name] + more]
+            fields += [(n, c_class(kind)) for n in [name] + more]
     assert fields == [("sums_dev", "pointer"), ("counts_dev", "pointer"), ("density_dev", "pointer"), ("pair_dev", "pointer"),
                       ("n_density_bins", "i32"), ("n_pair_bins", "i32"), ("lo", "f32"), ("hi", "f32")]
-    assert [(n, _ctypes_class(t)) for n, t in obs.ObserveAcc._fields_] == fields
+    assert [(n, ctypes_class(t)) for n, t in obs.ObserveAcc._fields_] == fields
     assert [getattr(obs.ObserveAcc, n).offset for n, _ in fields] == [0, 8, 16, 24, 32, 36, 40, 44]
     assert ctypes.sizeof(obs.ObserveAcc) == 48
 

@@ -3,16 +3,15 @@ identity its shift rests on, include/waveflow_sr_cg.h against sr.CG_PROTOTYPES a
 refuse before any launch, and that the default solver='cholesky' still makes the calls it made before."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 from waveflow_amd import _lib, sr, vqmc
+from abi_header import ctypes_class, header_prototypes, no_comments
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "waveflow_sr_cg.h")
-SCALAR = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "f32", "double": "f64"}
 NAMES = ["wf_sr_cg_workspace_bytes", "wf_sr_cg_solve"]
 
 
@@ -70,38 +69,22 @@ def test_cg_reference_edge_states():
     assert abs(steps[-1][0] - steps[-1][1]) <= 1e-12
 
 
-def _no_comments():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _c_class(text):
-    words = [w for w in text.replace("*", " * ").split() if w != "const"]
-    return "pointer" if "*" in words else SCALAR[words[0]]
-
-
-def _ctypes_class(t):
-    return {ctypes.c_void_p: "pointer", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
-
-
 def test_cg_prototype_table_matches_the_header_and_the_library():
-    declared = {}
-    for ret, name, args in re.findall(r"^([\w \*]+?)\b(wf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _no_comments(), flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        declared[name] = (_c_class(ret), [_c_class(a.rsplit(None, 1)[0] if "*" not in a else a) for a in args])
+    declared = header_prototypes(HEADER)
     assert list(declared) == list(sr.CG_PROTOTYPES) == NAMES
     raw = ctypes.CDLL(_lib.LIB_PATH)
     L = sr.lib()
     for name, (ret, args) in declared.items():
         assert hasattr(raw, name), name
         restype, argtypes = sr.CG_PROTOTYPES[name]
-        assert [_ctypes_class(t) for t in argtypes] == args, (name, args)
-        assert _ctypes_class(restype) == ret
+        assert [ctypes_class(t) for t in argtypes] == args, (name, args)
+        assert ctypes_class(restype) == ret
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == list(argtypes)
     assert declared["wf_sr_cg_solve"][1].count("f64") == 3 and declared["wf_sr_cg_solve"][1].count("i32") == 3
     assert not set(declared) & (set(_lib.PROTOTYPES) | set(sr.PROTOTYPES) | set(sr.STEP_PROTOTYPES) | set(sr.SPRING_PROTOTYPES))
     assert len(sr.PROTOTYPES) == 4 and len(sr.STEP_PROTOTYPES) == 2 and len(sr.SPRING_PROTOTYPES) == 5
-    assert '#include "waveflow_sr_spring.h"' in open(HEADER).read() and "WF_ABI_VERSION" not in _no_comments()
+    assert '#include "waveflow_sr_spring.h"' in open(HEADER).read() and "WF_ABI_VERSION" not in no_comments(HEADER)
     assert L.wf_abi_version() == 2
 
 

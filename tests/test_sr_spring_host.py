@@ -9,44 +9,17 @@ import numpy as np
 import pytest
 
 from waveflow_amd import _lib, core, sr, vqmc
+from abi_header import c_class, ctypes_class, header_prototypes, no_comments
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "waveflow_sr_spring.h")
-SCALAR = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "f32", "double": "f64"}
 NAMES = ["wf_sr_matvec", "wf_sr_apply_add", "wf_spring_rhs", "wf_vqmc_spring_step_workspace_bytes", "wf_vqmc_spring_step"]
-
-
-def _no_comments():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _c_class(text, is_return=False):
-    words = [w for w in text.replace("*", " * ").split() if w != "const"]
-    if "*" in words:
-        return "pointer"
-    return SCALAR[words[0]]   # KeyError: a type this test does not know
-
-
-def _header_prototypes():
-    out = {}
-    for ret, name, args in re.findall(r"^([\w \*]+?)\b(wf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _no_comments(), flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        assert name not in out, name
-        out[name] = (_c_class(ret, True), [_c_class(a.rsplit(None, 1)[0] if "*" not in a else a) for a in args])
-    return out
-
-
-def _ctypes_class(t):
-    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
-        return "pointer"
-    return {ctypes.c_void_p: "pointer", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64", ctypes.c_float: "f32",
-            ctypes.c_double: "f64"}[t]
 
 
 def test_spring_prototype_table_matches_the_header_and_the_library():
     """sr.SPRING_PROTOTYPES against the header: the same functions in the same order, per position the same argument class; every symbol
     exported; sr.lib() applies the table; the existing tables keep their sizes and the ABI version stays 2."""
-    declared = _header_prototypes()
+    declared = header_prototypes(HEADER)
     assert list(declared) == list(sr.SPRING_PROTOTYPES) == NAMES
     raw = ctypes.CDLL(_lib.LIB_PATH)
     L = sr.lib()
@@ -54,8 +27,8 @@ def test_spring_prototype_table_matches_the_header_and_the_library():
     for name, (ret, args) in declared.items():
         assert hasattr(raw, name), name
         restype, argtypes = sr.SPRING_PROTOTYPES[name]
-        assert [_ctypes_class(t) for t in argtypes] == args, (name, args)
-        assert _ctypes_class(restype) == ret, (name, ret)
+        assert [ctypes_class(t) for t in argtypes] == args, (name, args)
+        assert ctypes_class(restype) == ret, (name, ret)
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == list(argtypes), name
     assert declared["wf_vqmc_spring_step"][1].count("f64") == 5 and declared["wf_vqmc_spring_step"][1][2] == "u64"
@@ -63,22 +36,22 @@ def test_spring_prototype_table_matches_the_header_and_the_library():
     assert not set(declared) & (set(_lib.PROTOTYPES) | set(sr.PROTOTYPES) | set(sr.STEP_PROTOTYPES))
     assert len(_lib.PROTOTYPES) == 55 and len(sr.PROTOTYPES) == 4 and len(sr.STEP_PROTOTYPES) == 2
     hdr = open(HEADER).read()
-    assert '#include "waveflow_sr_step.h"' in hdr and "WF_ABI_VERSION" not in _no_comments()
+    assert '#include "waveflow_sr_step.h"' in hdr and "WF_ABI_VERSION" not in no_comments(HEADER)
     assert L.wf_abi_version() == 2
 
 
 def test_spring_state_struct_matches_the_header():
     """wf_spring_train_state: the fields of wf_sr_train_state in their order and at their offsets, then phi_dev and eff_ring_dev."""
-    body = re.search(r"typedef\s+struct\s+wf_spring_train_state\s*\{(.*?)\}\s*wf_spring_train_state\s*;", _no_comments(), flags=re.S).group(1)
+    body = re.search(r"typedef\s+struct\s+wf_spring_train_state\s*\{(.*?)\}\s*wf_spring_train_state\s*;", no_comments(HEADER), flags=re.S).group(1)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
         if decl:
             kind, name = decl.replace("*", " * ").rsplit(None, 1)
-            fields.append((name, _c_class(kind)))
-    old = [(n, _ctypes_class(t)) for n, t in sr.SrTrainState._fields_]
+            fields.append((name, c_class(kind)))
+    old = [(n, ctypes_class(t)) for n, t in sr.SrTrainState._fields_]
     assert fields == old + [("phi_dev", "pointer"), ("eff_ring_dev", "pointer")]
-    assert [(n, _ctypes_class(t)) for n, t in sr.SpringTrainState._fields_] == fields
+    assert [(n, ctypes_class(t)) for n, t in sr.SpringTrainState._fields_] == fields
     assert [getattr(sr.SpringTrainState, n).offset for n, _ in old] == [getattr(sr.SrTrainState, n).offset for n, _ in old]
     assert sr.SpringTrainState.phi_dev.offset == 56 and sr.SpringTrainState.eff_ring_dev.offset == 64 and ctypes.sizeof(sr.SpringTrainState) == 72
 

@@ -7,48 +7,16 @@ import re
 import pytest
 
 from waveflow_amd import _lib, core, sr, vqmc
+from abi_header import c_class, ctypes_class, header_prototypes, no_comments
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "waveflow_sr_step.h")
-SCALAR = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "f32", "double": "f64"}
-
-
-def _no_comments():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _c_class(text, is_return=False):
-    words = [w for w in text.replace("*", " * ").split() if w != "const"]
-    if "*" in words:
-        return "string" if is_return and words[0] == "char" else "pointer"
-    if is_return and words == ["void"]:
-        return "void"
-    return SCALAR[words[0]]   # KeyError: a type this test does not know
-
-
-def _header_prototypes():
-    """name -> (class of the return type, [class per argument]) for every wf_* function the header declares, in its order."""
-    out = {}
-    for ret, name, args in re.findall(r"^([\w \*]+?)\b(wf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _no_comments(), flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        assert name not in out, name
-        out[name] = (_c_class(ret, True), [] if args == ["void"] else [_c_class(a.rsplit(None, 1)[0] if "*" not in a else a) for a in args])
-    return out
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
-        return "pointer"
-    return {ctypes.c_void_p: "pointer", ctypes.c_char_p: "string", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64",
-            ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
 
 
 def test_step_prototype_table_matches_the_header_and_the_library():
     """sr.STEP_PROTOTYPES against include/waveflow_sr_step.h: the same functions in the same order, per position the same argument class; every
     symbol exported; sr.lib() applies the table; nothing of it is in the two existing tables, which keep their sizes; the ABI version stays 2."""
-    declared = _header_prototypes()
+    declared = header_prototypes(HEADER)
     assert list(declared) == list(sr.STEP_PROTOTYPES) == ["wf_vqmc_sr_step_workspace_bytes", "wf_vqmc_sr_step"]
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
@@ -58,8 +26,8 @@ def test_step_prototype_table_matches_the_header_and_the_library():
     for name, (ret, args) in declared.items():
         restype, argtypes = sr.STEP_PROTOTYPES[name]
         assert len(argtypes) == len(args), (name, len(argtypes), len(args))
-        assert [_ctypes_class(t) for t in argtypes] == args, (name, args)
-        assert _ctypes_class(restype) == ret, (name, ret)
+        assert [ctypes_class(t) for t in argtypes] == args, (name, args)
+        assert ctypes_class(restype) == ret, (name, ret)
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == list(argtypes), name
     assert declared["wf_vqmc_sr_step"][1].count("f64") == 2 and declared["wf_vqmc_sr_step"][1][2] == "u64"
@@ -67,22 +35,22 @@ def test_step_prototype_table_matches_the_header_and_the_library():
     assert not set(declared) & set(_lib.PROTOTYPES) and not set(declared) & set(sr.PROTOTYPES)
     assert len(_lib.PROTOTYPES) == 55 and len(sr.PROTOTYPES) == 4
     hdr = open(HEADER).read()
-    assert '#include "waveflow_sr.h"' in hdr and "WF_ABI_VERSION" not in _no_comments()
+    assert '#include "waveflow_sr.h"' in hdr and "WF_ABI_VERSION" not in no_comments(HEADER)
     assert L.wf_abi_version() == 2
 
 
 def test_state_struct_matches_the_header():
     """wf_sr_train_state field by field: six pointers, then two int32 -- names, order, kinds and offsets of sr.SrTrainState."""
-    body = re.search(r"typedef\s+struct\s+wf_sr_train_state\s*\{(.*?)\}\s*wf_sr_train_state\s*;", _no_comments(), flags=re.S).group(1)
+    body = re.search(r"typedef\s+struct\s+wf_sr_train_state\s*\{(.*?)\}\s*wf_sr_train_state\s*;", no_comments(HEADER), flags=re.S).group(1)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
         if decl:
             kind, name = decl.replace("*", " * ").rsplit(None, 1)
-            fields.append((name, _c_class(kind)))
+            fields.append((name, c_class(kind)))
     assert fields == [("params_dev", "pointer"), ("counter_dev", "pointer"), ("step_size_dev", "pointer"), ("loss_ring_dev", "pointer"),
                       ("norm_ring_dev", "pointer"), ("status_dev", "pointer"), ("ring_len", "i32"), ("defer_eval_tables", "i32")]
-    assert [(n, _ctypes_class(t)) for n, t in sr.SrTrainState._fields_] == fields
+    assert [(n, ctypes_class(t)) for n, t in sr.SrTrainState._fields_] == fields
     assert ctypes.sizeof(sr.SrTrainState) == 6 * 8 + 8
     assert [getattr(sr.SrTrainState, n).offset for n, _ in fields] == [0, 8, 16, 24, 32, 40, 48, 52]
 

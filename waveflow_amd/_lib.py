@@ -135,6 +135,30 @@ PROTOTYPES = {
 EXPORTS = list(PROTOTYPES)
 
 _lib = None
+# (handle, ids of the prototype tables applied to it).  An id names a table only while the table lives: the tables are the modules' PROTOTYPES
+# dicts, which live as long as the process -- pass no temporary dict to bound(), its id can be handed out again
+_bound = None
+
+
+def _apply(L, table):
+    for name, (restype, argtypes) in table.items():
+        f = getattr(L, name)
+        f.restype = restype
+        f.argtypes = argtypes
+
+
+def bound(*tables):
+    """The handle of lib() with these prototype tables (a module's PROTOTYPES: one table per header of include/) applied to it, each once
+    per handle.  Every module's lib() is one call of this."""
+    global _bound
+    L = lib()
+    if _bound is None or _bound[0] is not L:
+        _bound = (L, set())
+    for table in tables:
+        if id(table) not in _bound[1]:
+            _apply(L, table)
+            _bound[1].add(id(table))
+    return L
 
 
 def lib():
@@ -151,10 +175,7 @@ def lib():
         import sys
         print(f"waveflow_amd: experiment library {LIB_PATH}", file=sys.stderr)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        f = getattr(L, name)
-        f.restype = restype
-        f.argtypes = argtypes
+    _apply(L, PROTOTYPES)
     if L.wf_abi_version() != 2:
         raise ImportError("libwaveflow_hip ABI version mismatch")
     _lib = L

@@ -32,7 +32,6 @@ int check_energy_model(const wf_model* m) {
     if (m->desc.n_flow_layers > 0 && m->desc.layer_kind != WF_LAYER_IMADE) return WF_ERR_UNSUPPORTED;
     return WF_OK;
 }
-// proton positions of the Hamiltonian (at most 8, on the host); false: invalid arguments
 bool make_protons(const float* host, int n, Protons* out) {
     if (n < 0 || n > 8 || (n > 0 && !host)) return false;
     *out = Protons{};

@@ -4,20 +4,18 @@
 #include <cstdint>
 
 #include "../../include/waveflow_dmc.h"
-#include "wf_internal.h"
-#include "wf_layout.h"
-#include "wf_observe.h"
+#include "wf_accum.h"
 
 namespace wf {
 
 constexpr int64_t kDmcMaxWalkers = WF_DMC_MAX_WALKERS;
-constexpr int kDmcBlock = 256;                   // one lane per walker
+constexpr int kDmcBlock = kObsBlock;             // one lane per walker
 constexpr int kDmcScanTile = 1024;               // walkers per block of the comb's scan: 256 lanes x 4, at most 1024 blocks at 2^20
 constexpr int kDmcScanBlocksMax = (int)(kDmcMaxWalkers / kDmcScanTile);
 
 inline int64_t dmc_scan_blocks(int64_t B) { return (B + kDmcScanTile - 1) / kDmcScanTile; }
-// the record's block partials: the grid of wf_observe_accumulate (observe_blocks), 6 doubles per block
-inline int64_t dmc_accept_ws_bytes(int64_t B) { return align256(observe_blocks(B) * WF_DMC_RECORD * 8); }
+// the record's block partials (wf_accum.h): 6 sums per block, no counts
+inline int64_t dmc_accept_ws_bytes(int64_t B) { return partial_bytes(observe_blocks(B), WF_DMC_RECORD); }
 
 // the comb's workspace: offsets in bytes
 struct DmcCombLayout {

@@ -9,7 +9,8 @@
 
 namespace wf {
 
-constexpr int kFwPartial = 8;   // 8-byte words per block partial: sum and sum of squares of V_en and of V_ee, then the 4 counts
+constexpr int kFwSums = 4, kFwCounts = 4;        // sum and sum of squares of V_en and of V_ee; the 4 counts of wf_observe_accumulate
+constexpr int kFwPartial = kFwSums + kFwCounts;  // 8-byte words per block partial (wf_accum.h)
 
 // the update's workspace: offsets in bytes
 struct DmcFwLayout {
@@ -20,7 +21,7 @@ inline DmcFwLayout dmc_fw_layout(int64_t B, int n_slots) {
     Bump b;
     l.anc = b.take((int64_t)n_slots * B * 4);
     l.mark = b.take((int64_t)n_slots * B);
-    l.partials = b.take((int64_t)(n_slots + 1) * observe_blocks(B) * kFwPartial * 8);
+    l.partials = b.take(partial_bytes((int64_t)(n_slots + 1) * observe_blocks(B), kFwPartial));
     l.distinct = b.take((WF_DMC_FW_MAX_SLOTS + 1) * 8);   // per slot, then the measurement number of the call
     l.total = b.at;
     return l;

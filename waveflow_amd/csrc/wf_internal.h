@@ -154,6 +154,8 @@ struct Protons {
     float pos[8];
     int n;
 };
+// proton positions of the Hamiltonian (at most 8, on the host) -> *out; false: invalid arguments (wf_dispatch.cpp)
+bool make_protons(const float* host, int n, Protons* out);
 // local energy of large batches on the matrix cores (wf_kernels_etile.hip): D = 2, <= 64 bases, mean box, IMADE + Waveflow prior, ungated
 int64_t energy_tile_floats(int64_t B);
 bool energy_tile_fused(const MfmaDev* mdev);

@@ -3,8 +3,8 @@
 // the caller (wf_psi_coord_derivs in the step, wf_train_dmc.cpp).  One lane per walker everywhere.
 //
 // k_dmc_propose   one launch, B / 256 blocks.
-// k_dmc_accept    the grid of k_observe (observe_blocks: a function of B alone, grid-stride), fp64 lane sums in walker order, a fixed shuffle
-//                 tree per wave, the four waves in order through LDS, one partial per block; k_dmc_record adds the partials in block order.
+// k_dmc_accept    observe_blocks(B) blocks, grid-stride; the generation record in the one order of the project's fp64 sums (wf_accum.h): one
+//                 partial per block, k_dmc_record adds the partials in block order.
 // the comb        k_comb_wmax (block maxima of the valid weights) -> k_comb_scan (every block reduces the <= 1024 block maxima again, quantises
 //                 its 1024 weights and scans them in uint64) -> k_comb_src (every block scans the <= 1024 block totals again, finds the source
 //                 of its slots by two bounded binary searches and gathers into the workspace) -> k_comb_store (copies back, weights 1, largest
@@ -98,34 +98,12 @@ __global__ __launch_bounds__(kDmcBlock) void k_dmc_propose(const float* __restri
     flag[b] = ok ? 0 : 1;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;   // (lane 0)
-}
-
-// the block's partial of the record: lanes -> wave (fixed tree) -> waves in order (the order of k_observe)
-__device__ __forceinline__ void block_partial(const double (&s)[WF_DMC_RECORD], double* __restrict__ partial) {
-    __shared__ double red[kDmcBlock / 64][WF_DMC_RECORD];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < WF_DMC_RECORD; ++k) {
-        const double w = wave_sum(s[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-    __syncthreads();
-    if (tid < WF_DMC_RECORD) {
-        double t = red[0][tid];
-        for (int w = 1; w < kDmcBlock / 64; ++w) t += red[w][tid];
-        partial[(int64_t)blockIdx.x * WF_DMC_RECORD + tid] = t;
-    }
-}
-
 template <int D>
 __global__ __launch_bounds__(kDmcBlock) void k_dmc_accept(float* __restrict__ xg, float* __restrict__ psi, float* __restrict__ grad,
                                                           float* __restrict__ eloc, const float* __restrict__ xn, const float* __restrict__ psn,
                                                           const float* __restrict__ grn, const float* __restrict__ hdn,
                                                           const int32_t* __restrict__ flag, int64_t B, const Protons pr, const DmcParams p,
-                                                          const double* __restrict__ e_trial, double* __restrict__ wg, double* __restrict__ partial,
+                                                          const double* __restrict__ e_trial, double* __restrict__ wg, u64* __restrict__ partial,
                                                           double* __restrict__ logA_out, float* __restrict__ u_out, int32_t* __restrict__ acc_out) {
     const u64 step = p.counter ? p.counter[0] : p.step;
     const double et = e_trial[0];
@@ -206,14 +184,14 @@ __global__ __launch_bounds__(kDmcBlock) void k_dmc_accept(float* __restrict__ xg
         if (u_out) u_out[b] = u;
         if (acc_out) acc_out[b] = accept ? 1 : 0;
     }
-    block_partial(s, partial);
+    block_partial<WF_DMC_RECORD, 0>(s, nullptr, WF_DMC_RECORD, partial + (int64_t)blockIdx.x * WF_DMC_RECORD);
 }
 
 // wf_vqmc_dmc_init: e_loc of the walkers themselves, weight 1 or (a value that is not finite) 0, the record's first three sums
 template <int D>
 __global__ __launch_bounds__(kDmcBlock) void k_dmc_init_weights(const float* __restrict__ xg, const float* __restrict__ psi, const float* __restrict__ grad,
                                                                 const float* __restrict__ hdiag, int64_t B, const Protons pr,
-                                                                float* __restrict__ eloc, double* __restrict__ wg, double* __restrict__ partial) {
+                                                                float* __restrict__ eloc, double* __restrict__ wg, u64* __restrict__ partial) {
     double s[WF_DMC_RECORD];
 #pragma unroll
     for (int k = 0; k < WF_DMC_RECORD; ++k) s[k] = 0.0;
@@ -242,27 +220,13 @@ __global__ __launch_bounds__(kDmcBlock) void k_dmc_init_weights(const float* __r
             s[5] += 1.0;
         }
     }
-    block_partial(s, partial);
+    block_partial<WF_DMC_RECORD, 0>(s, nullptr, WF_DMC_RECORD, partial + (int64_t)blockIdx.x * WF_DMC_RECORD);
 }
 
-// One workgroup: thread k < 6 adds column k of the block partials in block order.  The partials pass through LDS 256 rows at a time (one
-// thread walking 1024 rows in global memory pays a memory latency per row: k_observe_reduce).
-constexpr int kRecordRows = 256;
-__global__ __launch_bounds__(kDmcBlock) void k_dmc_record(const double* __restrict__ partial, int n_blocks, double* __restrict__ record) {
-    __shared__ double stage[kRecordRows * WF_DMC_RECORD];
-    const int k = threadIdx.x;
-    double t = 0.0;
-    for (int b0 = 0; b0 < n_blocks; b0 += kRecordRows) {
-        const int rows = n_blocks - b0 < kRecordRows ? n_blocks - b0 : kRecordRows;
-        for (int i = k; i < rows * WF_DMC_RECORD; i += kDmcBlock) stage[i] = partial[(int64_t)b0 * WF_DMC_RECORD + i];
-        __syncthreads();
-        if (k < WF_DMC_RECORD) {
-#pragma unroll 8
-            for (int b = 0; b < rows; ++b) t += stage[b * WF_DMC_RECORD + k];
-        }
-        __syncthreads();
-    }
-    if (k < WF_DMC_RECORD) record[k] = t;
+// One workgroup: thread k < 6 gets column k of the block partials (reduce_columns): the record of this generation.
+__global__ __launch_bounds__(kDmcBlock) void k_dmc_record(const u64* __restrict__ partial, int n_blocks, double* __restrict__ record) {
+    const Column col = reduce_columns<WF_DMC_RECORD>(partial, n_blocks, WF_DMC_RECORD, WF_DMC_RECORD);
+    if (threadIdx.x < WF_DMC_RECORD) record[threadIdx.x] = col.sum;
 }
 
 // ---- the comb
@@ -485,15 +449,6 @@ __global__ void k_dmc_finish(const double* __restrict__ record, u64* __restrict_
     counter[0] = g + 1ull;
 }
 
-int finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_hip_error((int)e);
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
-}
-
 #define WF_DMC_CASES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 
 }  // namespace
@@ -512,7 +467,7 @@ int launch_dmc_propose(const float* x, const float* psi, const float* grad, int6
             return WF_ERR_INVALID;
     }
 #undef WF_DMC_X
-    return finish();
+    return launch_status();
 }
 
 int launch_dmc_accept(float* x, float* psi, float* grad, float* e_loc, const float* x_new, const float* psi_new, const float* grad_new,
@@ -520,7 +475,7 @@ int launch_dmc_accept(float* x, float* psi, float* grad, float* e_loc, const flo
                       double* w, double* record, double* logA, float* u, int32_t* accepted, int init, void* ws, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int64_t blocks = observe_blocks(B);
-    double* partial = (double*)ws;
+    u64* partial = (u64*)ws;
 #define WF_DMC_X(DD)                                                                                                                              \
     case DD:                                                                                                                                      \
         if (init)                                                                                                                                 \
@@ -536,8 +491,8 @@ int launch_dmc_accept(float* x, float* psi, float* grad, float* e_loc, const flo
             return WF_ERR_INVALID;
     }
 #undef WF_DMC_X
-    hipLaunchKernelGGL(k_dmc_record, dim3(1), dim3(kDmcBlock), 0, s, (const double*)partial, (int)blocks, record);
-    return finish();
+    hipLaunchKernelGGL(k_dmc_record, dim3(1), dim3(kDmcBlock), 0, s, (const u64*)partial, (int)blocks, record);
+    return launch_status();
 }
 
 int launch_dmc_reconfigure(float* x, float* psi, float* grad, float* e_loc, double* w, int64_t B, int D, const DmcParams& p, int purpose,
@@ -567,25 +522,25 @@ int launch_dmc_reconfigure(float* x, float* psi, float* grad, float* e_loc, doub
             return WF_ERR_INVALID;
     }
 #undef WF_DMC_X
-    return finish();
+    return launch_status();
 }
 
 int launch_dmc_reset(const wf_dmc_state* st, void* stream) {
     const int n = st->ring_len * WF_DMC_RING_RECORD;
     hipLaunchKernelGGL(k_dmc_reset, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (u64*)st->counter_dev, (u64*)st->status_dev,
                        st->ring_dev, n);
-    return finish();
+    return launch_status();
 }
 
 int launch_dmc_trial_from_record(const double* record, double* e_trial, void* stream) {
     hipLaunchKernelGGL(k_dmc_trial, dim3(1), dim3(1), 0, (hipStream_t)stream, record, e_trial);
-    return finish();
+    return launch_status();
 }
 
 int launch_dmc_finish(const wf_dmc_state* st, const double* record, int64_t B, double tau, void* stream) {
     hipLaunchKernelGGL(k_dmc_finish, dim3(1), dim3(1), 0, (hipStream_t)stream, record, (u64*)st->counter_dev, st->e_trial_dev, st->ring_dev,
                        st->ring_len, (double)B, tau);
-    return finish();
+    return launch_status();
 }
 
 }  // namespace wf
@@ -625,16 +580,14 @@ int wf_dmc_accept(float* x_dev, float* psi_dev, float* grad_dev, float* e_loc_de
                   void* workspace_dev, int64_t workspace_bytes, void* stream) {
     const int rc = dmc_check_common(B, n_dim, tau);
     if (rc) return rc;
-    if (n_protons < 0 || n_protons > 8 || (n_protons > 0 && !protons_host) || !std::isfinite(e_cut) || e_cut < 0.0) return WF_ERR_INVALID;
+    Protons pr{};
+    if (!make_protons(protons_host, n_protons, &pr) || !std::isfinite(e_cut) || e_cut < 0.0) return WF_ERR_INVALID;
     if (B == 0) return WF_OK;
     if (!x_dev || !psi_dev || !grad_dev || !e_loc_dev || !x_new_dev || !psi_new_dev || !grad_new_dev || !hdiag_new_dev || !flag_dev || !e_trial_dev ||
         !w_dev || !record_dev)
         return WF_ERR_INVALID;
     if (!workspace_dev || workspace_bytes < dmc_accept_ws_bytes(B)) return WF_ERR_INVALID;
     if (wf_device_count() <= 0) return WF_ERR_NO_DEVICE;
-    Protons pr{};
-    pr.n = n_protons;
-    for (int i = 0; i < n_protons; ++i) pr.pos[i] = protons_host[i];
     const DmcParams p{tau, std::sqrt(tau), e_cut, 0.0f, limit_drift != 0, (unsigned long long)seed, (unsigned long long)step, nullptr};
     return launch_dmc_accept(x_dev, psi_dev, grad_dev, e_loc_dev, x_new_dev, psi_new_dev, grad_new_dev, hdiag_new_dev, flag_dev, B, n_dim, pr, p,
                              e_trial_dev, w_dev, record_dev, logA_dev, u_dev, accepted_dev, 0, workspace_dev, stream);

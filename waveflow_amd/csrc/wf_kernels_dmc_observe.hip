@@ -6,15 +6,13 @@
 //   k_fw_compose  (walker blocks x slots)   tmp[s][k] = anc[s][clamp(src[k])] for the non-empty slots, into the workspace; the marks of the
 //                                           distinct-ancestor count and its counters zeroed; when measuring, the series row zeroed and the
 //                                           measurement number copied for the last launch
-//   k_fw_measure  (walker blocks x lags)    the accumulation of k_observe (wf_kernels_observe.hip) for one lag per workgroup: lag 0 reads x,
-//                                           the workgroups of slot s read snap[s][tmp[s][k]] and mark tmp[s][k] as seen; LDS histograms as
-//                                           uint32 (a block sees at most 2^20 / 1024 * 28 increments per bin), block partials in the workspace
+//   k_fw_measure  (walker blocks x lags)    the accumulation of wf_accum.h for one lag per workgroup: lag 0 reads x, the workgroups of slot s
+//                                           read snap[s][tmp[s][k]] and mark tmp[s][k] as seen; LDS histograms as uint32 (a block sees at
+//                                           most 2^20 / 1024 * 28 increments per bin), block partials in the workspace
 //   k_fw_store    (walker blocks x slots)   anc <- tmp; when measuring: the marks counted (integers), and slot s* retagged: snap <- x, anc <- k
-//   k_fw_reduce   (one workgroup per lag)   the partials in block order -> sums and counts (k_observe_reduce's staging through LDS), the
-//                                           series row, tag[s*] <- g, measurements + 1
-// The fp64 sums follow k_observe's order (lane sums in k order over observe_blocks(B) blocks, a fixed shuffle tree per wave, waves in order,
-// blocks in order, one thread adds): no floating-point atomics.  The potentials are those of wf_eloc.h (local_values with psi = 1 and no
-// derivatives: the terms that are not asked for fold away).
+//   k_fw_reduce   (one workgroup per lag)   the partials in block order -> sums and counts, the series row, tag[s*] <- g, measurements + 1
+// The fp64 sums are formed in the one order of the project (wf_accum.h), per lag over the walker index k.  The potentials are those of
+// wf_eloc.h (local_values with psi = 1 and no derivatives: the terms that are not asked for fold away).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -32,19 +30,9 @@ constexpr u64 kFwEmpty = WF_DMC_FW_EMPTY;
 constexpr int kFwCopySlot = WF_DMC_FW_MAX_SLOTS;   // word of the `distinct` area that holds the measurement number of this call
 
 struct FwGeom {
-    int nd, np;                 // bins (0: no such histogram)
-    float lo, scale_d, scale_p;
+    HistGeom h;
     int n_slots, stride, series_len;
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;   // (lane 0)
-}
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // the lag slot s serves in generation g, or -1 (empty, tagged in the future, or a lag outside 1 .. n_slots)
 __device__ __forceinline__ int served_lag(u64 tag, u64 g, const FwGeom& q) {
@@ -82,8 +70,6 @@ __global__ __launch_bounds__(kObsBlock) void k_fw_measure(const float* __restric
                                                           unsigned char* __restrict__ mark, const u64* __restrict__ gen, const Protons pr,
                                                           const FwGeom q, u64* __restrict__ partial, u64* __restrict__ density, u64* __restrict__ pair) {
     extern __shared__ unsigned int hist[];   // [D][nd] density, then [np] pair
-    __shared__ double red[kObsBlock / 64][4];
-    __shared__ u64 redc[kObsBlock / 64][4];
     const u64 g = gen[0];
     if (g % (u64)q.stride != 0) return;   // (uniform over the grid)
     const int y = blockIdx.y, tid = threadIdx.x;
@@ -98,13 +84,9 @@ __global__ __launch_bounds__(kObsBlock) void k_fw_measure(const float* __restric
         idx = tmp + (int64_t)(y - 1) * B;
         seen = mark + (int64_t)(y - 1) * B;
     }
-    const int n_hist = D * q.nd + q.np;
-    for (int i = tid; i < n_hist; i += kObsBlock) hist[i] = 0u;
-    __syncthreads();
-    unsigned int* hpair = hist + D * q.nd;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    hist_clear(hist, D * q.h.nd + q.h.np);
+    double s[kFwSums] = {0.0, 0.0, 0.0, 0.0};
     u64 n_ok = 0, n_skip = 0, out_d = 0, out_p = 0;
-    const float nd_f = (float)q.nd, np_f = (float)q.np;
     const float zero[D] = {};
     for (int64_t k = (int64_t)blockIdx.x * kObsBlock + tid; k < B; k += (int64_t)gridDim.x * kObsBlock) {
         int64_t a = k;
@@ -132,66 +114,11 @@ __global__ __launch_bounds__(kObsBlock) void k_fw_measure(const float* __restric
         s[1] += en * en;
         s[2] += ee;
         s[3] += ee * ee;
-        if (q.nd > 0) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                const float t = __fmul_rn(__fsub_rn(x[d], q.lo), q.scale_d);
-                if (t >= 0.0f && t < nd_f)
-                    atomicAdd(&hist[d * q.nd + (int)t], 1u);
-                else
-                    out_d += 1;
-            }
-        }
-        if (q.np > 0) {
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < i; ++j) {
-                    const float t = __fmul_rn(fabsf(__fsub_rn(x[i], x[j])), q.scale_p);
-                    if (t >= 0.0f && t < np_f)
-                        atomicAdd(&hpair[(int)t], 1u);
-                    else
-                        out_p += 1;
-                }
-        }
+        hist_add<D>(x, q.h, hist, out_d, out_p);
     }
-    // the block's partial: lanes -> wave (fixed tree) -> waves in order
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double w = wave_sum(s[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-    u64 c[4] = {n_ok, n_skip, out_d, out_p};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const u64 w = wave_sum(c[k]);
-        if (lane == 0) redc[wave][k] = w;
-    }
-    __syncthreads();   // (also: every LDS histogram update of the block has landed)
-    if (tid < kFwPartial) {
-        u64* row = partial + ((int64_t)y * gridDim.x + blockIdx.x) * kFwPartial;   // the sums as their bit patterns, then the counts
-        if (tid < 4) {
-            double t = red[0][tid];
-            for (int w = 1; w < kObsBlock / 64; ++w) t += red[w][tid];
-            row[tid] = (u64)__double_as_longlong(t);
-        } else {
-            u64 t = 0;
-            for (int w = 0; w < kObsBlock / 64; ++w) t += redc[w][tid - 4];
-            row[tid] = t;
-        }
-    }
-    // non-zero bins -> the lag's 64-bit histograms
-    u64* dens = density + (int64_t)lag * D * q.nd;
-    u64* prs = pair + (int64_t)lag * q.np;
-    for (int i = tid; i < D * q.nd; i += kObsBlock) {
-        const unsigned int n = hist[i];
-        if (n) atomicAdd(&dens[i], (u64)n);
-    }
-    for (int i = tid; i < q.np; i += kObsBlock) {
-        const unsigned int n = hpair[i];
-        if (n) atomicAdd(&prs[i], (u64)n);
-    }
+    const u64 c[kFwCounts] = {n_ok, n_skip, out_d, out_p};
+    block_partial<kFwSums, kFwCounts>(s, c, kFwSums, partial + ((int64_t)y * gridDim.x + blockIdx.x) * kFwPartial);
+    hist_flush<D>(hist, q.h, density + (int64_t)lag * D * q.h.nd, pair + (int64_t)lag * q.h.np);   // the lag's 64-bit histograms
 }
 
 template <int D>
@@ -229,35 +156,20 @@ __global__ __launch_bounds__(kDmcBlock) void k_fw_store(const float* __restrict_
 }
 
 // One workgroup per lag slot y (0: the current walkers; s + 1: slot s).  Thread k < 8 adds column k of the slot's block partials in block
-// order (staged through LDS as k_observe_reduce does), then adds it to the accumulator of the lag the slot serves and writes the series row.
-constexpr int kFwReduceRows = 256;
+// order (reduce_columns), then adds it to the accumulator of the lag the slot serves and writes the series row.
 __global__ __launch_bounds__(kObsBlock) void k_fw_reduce(const u64* __restrict__ partial, int n_blocks, int64_t B, u64* __restrict__ tag,
                                                          const u64* __restrict__ distinct, double* __restrict__ sums, u64* __restrict__ counts,
                                                          double* __restrict__ series, u64* __restrict__ measurements, const u64* __restrict__ gen,
                                                          const FwGeom q) {
-    __shared__ u64 stage[kFwReduceRows * kFwPartial];
     const u64 g = gen[0];
     if (g % (u64)q.stride != 0) return;   // (uniform over the grid)
     const int y = blockIdx.x, k = threadIdx.x;
     const int lag = y == 0 ? 0 : served_lag(tag[y - 1], g, q);   // (uniform over the block)
     __syncthreads();                                             // every thread holds the old tag before thread 0 replaces it (below)
     if (lag >= 0) {
-        const u64* mine = partial + (int64_t)y * n_blocks * kFwPartial;
-        double t = 0.0;
-        u64 c = 0;
-        for (int b0 = 0; b0 < n_blocks; b0 += kFwReduceRows) {
-            const int rows = n_blocks - b0 < kFwReduceRows ? n_blocks - b0 : kFwReduceRows;
-            for (int i = k; i < rows * kFwPartial; i += kObsBlock) stage[i] = mine[(int64_t)b0 * kFwPartial + i];
-            __syncthreads();
-            if (k < 4) {
-#pragma unroll 8
-                for (int b = 0; b < rows; ++b) t += __longlong_as_double((long long)stage[b * kFwPartial + k]);
-            } else if (k < kFwPartial) {
-#pragma unroll 8
-                for (int b = 0; b < rows; ++b) c += stage[b * kFwPartial + k];
-            }
-            __syncthreads();
-        }
+        const Column col = reduce_columns<kFwPartial>(partial + (int64_t)y * n_blocks * kFwPartial, n_blocks, kFwPartial, kFwSums);
+        const double t = col.sum;
+        const u64 c = col.count;
         double* row = series + ((size_t)(distinct[kFwCopySlot] % (u64)q.series_len) * (q.n_slots + 1) + lag) * WF_DMC_FW_SERIES;
         if (k < 4) {
             sums[lag * 4 + k] += t;
@@ -275,43 +187,23 @@ __global__ __launch_bounds__(kObsBlock) void k_fw_reduce(const u64* __restrict__
     }
 }
 
-int finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_hip_error((int)e);
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
-}
-
 #define WF_FW_CASES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 
 }  // namespace
 
 int dmc_fw_check(const wf_dmc_fw* fw) {
     if (!fw || fw->n_slots < 1 || fw->n_slots > WF_DMC_FW_MAX_SLOTS || fw->stride < 1 || fw->series_len < 1) return WF_ERR_INVALID;
-    if (fw->n_density_bins < 0 || fw->n_pair_bins < 0) return WF_ERR_INVALID;
-    if (!std::isfinite(fw->lo) || !std::isfinite(fw->hi) || !(fw->lo < fw->hi) || !std::isfinite(fw->hi - fw->lo)) return WF_ERR_INVALID;
+    // (a range that is no range is refused in front of bins beyond the limits, unlike wf_observe_accumulate: the header's order)
+    if (!hist_range_ok(fw->lo, fw->hi)) return WF_ERR_INVALID;
     if (!fw->snap_dev || !fw->anc_dev || !fw->tag_dev || !fw->counts_dev || !fw->sums_dev || !fw->measurements_dev || !fw->series_dev)
         return WF_ERR_INVALID;
-    if (fw->n_density_bins > kObsMaxDensityBins || fw->n_pair_bins > kObsMaxPairBins) return WF_ERR_UNSUPPORTED;
-    if ((fw->n_density_bins > 0 && !fw->density_dev) || (fw->n_pair_bins > 0 && !fw->pair_dev)) return WF_ERR_INVALID;
-    return WF_OK;
+    return hist_check(fw->n_density_bins, fw->n_pair_bins, fw->lo, fw->hi, fw->density_dev, fw->pair_dev);
 }
 
 int launch_dmc_fw_update(const float* x, const int32_t* src, int64_t B, int D, const Protons& pr, const wf_dmc_fw* fw, const u64* generation,
                          void* ws, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    FwGeom q{};
-    q.nd = fw->n_density_bins;
-    q.np = fw->n_pair_bins;
-    q.lo = fw->lo;
-    const float width = fw->hi - fw->lo;
-    q.scale_d = (float)q.nd / width;
-    q.scale_p = (float)q.np / width;
-    q.n_slots = fw->n_slots;
-    q.stride = fw->stride;
-    q.series_len = fw->series_len;
+    const FwGeom q{make_hist_geom(fw->n_density_bins, fw->n_pair_bins, fw->lo, fw->hi), fw->n_slots, fw->stride, fw->series_len};
     const DmcFwLayout l = dmc_fw_layout(B, q.n_slots);
     char* base = (char*)ws;
     int32_t* tmp = (int32_t*)(base + l.anc);
@@ -322,7 +214,7 @@ int launch_dmc_fw_update(const float* x, const int32_t* src, int64_t B, int D, c
     const int n_blocks = (int)observe_blocks(B);
     const dim3 lanes((unsigned)((B + kDmcBlock - 1) / kDmcBlock), (unsigned)q.n_slots);
     const dim3 lags((unsigned)n_blocks, (unsigned)(q.n_slots + 1));
-    const size_t lds = ((size_t)D * q.nd + q.np) * sizeof(unsigned int);
+    const size_t lds = ((size_t)D * q.h.nd + q.h.np) * sizeof(unsigned int);
     hipLaunchKernelGGL(k_fw_compose, lanes, dim3(kDmcBlock), 0, st, src, B, (const int32_t*)fw->anc_dev, (const u64*)tag, tmp, mark, distinct,
                        generation, (const u64*)measurements, fw->series_dev, q);
 #define WF_FW_X(DD)                                                                                                                           \
@@ -340,7 +232,7 @@ int launch_dmc_fw_update(const float* x, const int32_t* src, int64_t B, int D, c
 #undef WF_FW_X
     hipLaunchKernelGGL(k_fw_reduce, dim3((unsigned)(q.n_slots + 1)), dim3(kObsBlock), 0, st, (const u64*)partial, n_blocks, B, tag,
                        (const u64*)distinct, fw->sums_dev, counts, fw->series_dev, measurements, generation, q);
-    return finish();
+    return launch_status();
 }
 
 }  // namespace wf
@@ -357,7 +249,8 @@ int64_t wf_dmc_fw_workspace_bytes(int64_t B, int32_t n_dim, int32_t n_slots) {
 
 int wf_dmc_fw_update(const float* x_dev, const int32_t* src_dev, int64_t B, int32_t n_dim, const float* protons_host, int32_t n_protons,
                      const wf_dmc_fw* fw, const uint64_t* generation_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
-    if (B < 0 || n_dim < 2 || n_dim > 8 || n_protons < 0 || n_protons > 8 || (n_protons > 0 && !protons_host)) return WF_ERR_INVALID;
+    Protons pr{};
+    if (B < 0 || n_dim < 2 || n_dim > 8 || !make_protons(protons_host, n_protons, &pr)) return WF_ERR_INVALID;
     const int rc = dmc_fw_check(fw);
     if (rc) return rc;
     if (B == 0) return WF_OK;
@@ -365,9 +258,6 @@ int wf_dmc_fw_update(const float* x_dev, const int32_t* src_dev, int64_t B, int3
     if (!x_dev || !generation_dev) return WF_ERR_INVALID;
     if (!workspace_dev || workspace_bytes < dmc_fw_layout(B, fw->n_slots).total) return WF_ERR_INVALID;
     if (wf_device_count() <= 0) return WF_ERR_NO_DEVICE;
-    Protons pr{};
-    pr.n = n_protons;
-    for (int i = 0; i < n_protons; ++i) pr.pos[i] = protons_host[i];
     return launch_dmc_fw_update(x_dev, src_dev, B, n_dim, pr, fw, (const unsigned long long*)generation_dev, workspace_dev, stream);
 }
 

@@ -2,11 +2,10 @@
 // reference rows on the walkers of psi (fp32, one rounding per operation, spelled with the _rn intrinsics), their fp64 moments, and the
 // overlap-penalised local energies.
 //
-// k_overlap: one lane per walker in 256-lane workgroups, a grid-stride loop over the grid of k_observe (observe_blocks: a function of B alone).
-// Memory-streaming: psi is read once, the K reference rows coalesced (lane = walker), a runtime loop over K.  The fp64 sums: each lane adds its
-// walkers in index order, a fixed shuffle tree per wave, the four waves in order through LDS, one partial per block in the workspace.
-// k_overlap_reduce (one workgroup, one thread per column) adds the partials in block order and then adds them to the accumulator.  No
-// floating-point atomics anywhere.  (tests/test_gpu_overlap.py holds the sums to overlap.reference_accumulate, which restates this order.)
+// k_overlap: one lane per walker in 256-lane workgroups, a grid-stride loop over observe_blocks(B) blocks.  Memory-streaming: psi is read
+// once, the K reference rows coalesced (lane = walker), a runtime loop over K.  The fp64 sums are formed in the one order of the project
+// (wf_accum.h): block partials in the workspace, k_overlap_reduce (one workgroup, one thread per column) adds them in block order and then
+// adds them to the accumulator.  (tests/test_gpu_overlap.py holds the sums to overlap.reference_accumulate, which restates that order.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,19 +24,8 @@ struct Lambdas {
     double v[kMaxK];
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;   // (lane 0)
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(kObsBlock) void k_overlap(const float* __restrict__ psi, const float* __restrict__ ref, int64_t ld, int64_t B, int K,
                                                        int has_acc, float* __restrict__ ratios, unsigned long long* __restrict__ partial) {
-    __shared__ double red[kObsBlock / 64][2 * kMaxK];
-    __shared__ unsigned long long redc[kObsBlock / 64][2];
     const int tid = threadIdx.x;
     double s[2 * kMaxK];
 #pragma unroll
@@ -74,63 +62,21 @@ __global__ __launch_bounds__(kObsBlock) void k_overlap(const float* __restrict__
         }
     }
     if (!has_acc) return;   // (uniform)
-    // the block's partial: lanes -> wave (fixed tree) -> waves in order
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < 2 * kMaxK; ++k) {
-        const double w = wave_sum(s[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
     const unsigned long long c[2] = {n_ok, n_skip};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const unsigned long long w = wave_sum(c[k]);
-        if (lane == 0) redc[wave][k] = w;
-    }
-    __syncthreads();
-    const int words = 2 * K + 2;
-    if (tid < words) {
-        unsigned long long* row = partial + (int64_t)blockIdx.x * words;   // 8-byte words: the sums as their bit patterns, then the counts
-        if (tid < 2 * K) {
-            double t = red[0][tid];
-            for (int w = 1; w < kObsBlock / 64; ++w) t += red[w][tid];
-            row[tid] = (unsigned long long)__double_as_longlong(t);
-        } else {
-            unsigned long long t = 0;
-            for (int w = 0; w < kObsBlock / 64; ++w) t += redc[w][tid - 2 * K];
-            row[tid] = t;
-        }
-    }
+    block_partial<2 * kMaxK, 2>(s, c, 2 * K, partial + (int64_t)blockIdx.x * overlap_partial_words(K));
 }
 
-// One workgroup: thread c < 2 K + 2 adds column c of the block partials in block order, then adds it to the accumulator; the step's counter + 1.
-// The partials pass through LDS, 256 rows (36 KB at K = 8) at a time, as in k_observe_reduce.
-constexpr int kReduceRows = 256;
+// One workgroup: thread c < 2 K + 2 gets column c of the block partials (reduce_columns) and adds it to the accumulator; the step's counter + 1.
 __global__ __launch_bounds__(kObsBlock) void k_overlap_reduce(const unsigned long long* __restrict__ partial, int n_blocks, int K, double* __restrict__ sums,
                                                               unsigned long long* __restrict__ counts, unsigned long long* __restrict__ counter) {
-    __shared__ unsigned long long stage[kReduceRows * kMaxWords];
     const int c = threadIdx.x;
-    const int words = 2 * K + 2;
-    double t = 0.0;
-    unsigned long long n = 0;
-    for (int b0 = 0; b0 < n_blocks; b0 += kReduceRows) {
-        const int rows = n_blocks - b0 < kReduceRows ? n_blocks - b0 : kReduceRows;
-        for (int i = c; i < rows * words; i += kObsBlock) stage[i] = partial[(int64_t)b0 * words + i];
-        __syncthreads();
-        if (c < 2 * K) {
-#pragma unroll 8
-            for (int b = 0; b < rows; ++b) t += __longlong_as_double((long long)stage[b * words + c]);
-        } else if (c < words) {
-#pragma unroll 8
-            for (int b = 0; b < rows; ++b) n += stage[b * words + c];
-        }
-        __syncthreads();
-    }
+    const int words = overlap_partial_words(K);
+    const Column col = reduce_columns<kMaxWords>(partial, n_blocks, words, 2 * K);
     if (n_blocks > 0) {
         if (c < 2 * K)
-            sums[c] += t;
+            sums[c] += col.sum;
         else if (c < words)
-            counts[c - 2 * K] += n;
+            counts[c - 2 * K] += col.count;
     }
     if (counter && c == 0) counter[0] += 1ull;
 }
@@ -161,15 +107,6 @@ __global__ __launch_bounds__(kObsBlock) void k_overlap_penalise(const float* e, 
     }
 }
 
-int finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_hip_error((int)e);
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
-}
-
 }  // namespace
 
 int launch_overlap(const float* psi, const float* ref, int64_t ld, int64_t B, int K, const wf_overlap_acc* acc, float* ratios, void* ws,
@@ -181,7 +118,7 @@ int launch_overlap(const float* psi, const float* ref, int64_t ld, int64_t B, in
     if (acc || counter)
         hipLaunchKernelGGL(k_overlap_reduce, dim3(1), dim3(kObsBlock), 0, s, partial, acc ? (int)blocks : 0, K, acc ? acc->sums_dev : nullptr,
                            acc ? (unsigned long long*)acc->counts_dev : nullptr, counter);
-    return finish();
+    return launch_status();
 }
 
 }  // namespace wf
@@ -226,7 +163,7 @@ int wf_overlap_penalise(const float* e_dev, const float* ratios_dev, int64_t ld,
     if (wf_device_count() <= 0) return WF_ERR_NO_DEVICE;
     hipLaunchKernelGGL(k_overlap_penalise, dim3((unsigned)observe_blocks(B)), dim3(kObsBlock), 0, (hipStream_t)stream, e_dev, ratios_dev, ld, B, (int)K, lam,
                        acc->sums_dev, (const unsigned long long*)acc->counts_dev, out_dev);
-    return finish();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -161,7 +161,6 @@ int apply_params(wf_model* m, const float* flat_dev, void* stream, bool eval_tab
 bool f16_overflow(const wf_model* cm);
 
 // ---- wf_dispatch.cpp: path predicates and chunk loops the training steps share with the entry points
-bool make_protons(const float* host, int n, Protons* out);
 bool grad_supported(const wf_model* m, bool second_order);
 int check_energy_model(const wf_model* m);
 bool step_reads_eval_tables(const wf_model* m, int64_t B);

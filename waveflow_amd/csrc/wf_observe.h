@@ -1,22 +1,19 @@
 // wf_observe.h -- what wf_kernels_observe.hip (the accumulation kernels, wf_observe_accumulate) and wf_train_observe.cpp (the measurement step)
-// share: the grid rule, the argument check of an accumulator and the launcher behind both entries.
+// share: the words of a block partial (the grid rule and the order of the sums: wf_accum.h), the argument check of an accumulator, the
+// launcher behind both entries, and the batch sizes a measurement step draws walkers for (wf_train_overlap.cpp asks too).
 #pragma once
 #include <cstdint>
 
 #include "../../include/waveflow_observe.h"
-#include "wf_internal.h"
+#include "wf_accum.h"
 
 namespace wf {
 
-constexpr int kObsBlock = 256;            // one lane per walker
-constexpr int64_t kObsMaxBlocks = 1024;   // the grid-stride loop takes the rest: the block partials stay within 112 KB
-constexpr int kObsPartial = 14;           // 8-byte words per block partial: 10 sums, 4 counts
-constexpr int kObsMaxDensityBins = 512, kObsMaxPairBins = 1024;
+constexpr int kObsSums = 10, kObsCounts = 4;
+constexpr int kObsPartial = kObsSums + kObsCounts;   // 8-byte words per block partial
 constexpr int64_t kObsMaxWalkers = (int64_t)1 << 36;   // per call: a block then sees at most 2^26 walkers of 28 pairs, which a uint32 LDS bin holds
 
-// blocks of the accumulation launch: a function of B alone
-inline int64_t observe_blocks(int64_t B) { return B < 1 ? 0 : (B + kObsBlock - 1) / kObsBlock < kObsMaxBlocks ? (B + kObsBlock - 1) / kObsBlock : kObsMaxBlocks; }
-inline int64_t observe_ws_bytes(int64_t B) { return (observe_blocks(B) * kObsPartial * 8 + 255) / 256 * 256; }
+inline int64_t observe_ws_bytes(int64_t B) { return partial_bytes(observe_blocks(B), kObsPartial); }
 
 // WF_OK, or what wf_observe_accumulate returns for this accumulator (acc != nullptr)
 int observe_check_acc(const wf_observe_acc* acc);
@@ -25,5 +22,9 @@ int observe_check_acc(const wf_observe_acc* acc);
 // counter, if given, is advanced by one behind them (the measurement step's last act, in the launch that adds the block partials).
 int launch_observe(const float* x, const float* psi, const float* grad, const float* hdiag, int64_t B, int D, const Protons& pr,
                    const wf_observe_acc* acc, float* values, void* ws, unsigned long long* counter, void* stream);
+
+// A sampler for B walkers, as a training step has one: the staged sampler where it applies (step_sampler_bytes is non-zero exactly there),
+// the wave sampler up to its limit.  current: at call time the staged sampler also needs fresh tables, as sample_step_walkers decides.
+bool measure_batch_covered(const wf_model* m, int64_t B, bool current);
 
 }  // namespace wf

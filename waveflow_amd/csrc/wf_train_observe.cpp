@@ -33,22 +33,21 @@ ObserveStepLayout observe_step_layout(const wf_model* m, int64_t batch) {
 
 // the models of wf_psi_coord_derivs whose walkers wf_observe_accumulate takes
 bool observe_model_covered(const wf_model* m) { return check_energy_model(m) == WF_OK && m->desc.n_dim >= 2 && m->desc.n_dim <= 8; }
-// a sampler for B walkers, as a training step has one: the staged sampler where it applies (step_sampler_bytes is non-zero exactly there),
-// the wave sampler up to its limit.  current: at call time the staged sampler also needs fresh tables, as sample_step_walkers decides.
-bool observe_batch_covered(const wf_model* m, int64_t B, bool current) {
+
+}  // namespace
+
+bool wf::measure_batch_covered(const wf_model* m, int64_t B, bool current) {
     if (B <= kWaveSampleMax) return true;
     if (B > kObsMaxWalkers) return false;
     if (step_sampler_bytes(m, B) == 0) return false;
     return !current || (!m->eval_tables_stale && !f16_overflow(m));
 }
 
-}  // namespace
-
 extern "C" {
 
 int64_t wf_vqmc_observe_step_workspace_bytes(const wf_model* m, int64_t batch) {
     if (!m || batch < 1) return WF_ERR_INVALID;
-    if (!observe_model_covered(m) || !observe_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
+    if (!observe_model_covered(m) || !measure_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
     return observe_step_layout(m, batch).total;
 }
 
@@ -62,7 +61,7 @@ int wf_vqmc_observe_step(const wf_model* m, const wf_observe_acc* acc, uint64_t*
         const int rc = observe_check_acc(acc);
         if (rc) return rc;
     }
-    if (!observe_model_covered(m) || !observe_batch_covered(m, batch, true)) return WF_ERR_UNSUPPORTED;
+    if (!observe_model_covered(m) || !measure_batch_covered(m, batch, true)) return WF_ERR_UNSUPPORTED;
     if (!m->params_set || !workspace_dev) return WF_ERR_INVALID;
     const ObserveStepLayout l = observe_step_layout(m, batch);
     if (workspace_bytes < l.total) return WF_ERR_INVALID;

@@ -31,14 +31,6 @@ OverlapStepLayout overlap_step_layout(const wf_model* m, int64_t batch, int K) {
 
 // the models the measurement steps draw walkers for (wf_train_observe.cpp: those of the energy sweeps, whose tables the samplers read)
 bool overlap_model_covered(const wf_model* m) { return check_energy_model(m) == WF_OK; }
-// a sampler for B walkers, as wf_vqmc_observe_step has one: the staged sampler where it applies (step_sampler_bytes is non-zero exactly there),
-// the wave sampler up to its limit.  current: at call time the staged sampler also needs fresh tables, as sample_step_walkers decides.
-bool overlap_batch_covered(const wf_model* m, int64_t B, bool current) {
-    if (B <= kWaveSampleMax) return true;
-    if (B > kObsMaxWalkers) return false;
-    if (step_sampler_bytes(m, B) == 0) return false;
-    return !current || (!m->eval_tables_stale && !f16_overflow(m));
-}
 
 }  // namespace
 
@@ -47,7 +39,7 @@ extern "C" {
 int64_t wf_vqmc_overlap_step_workspace_bytes(const wf_model* m, int64_t batch, int32_t K) {
     if (!m || batch < 1 || K < 1) return WF_ERR_INVALID;
     if (K > WF_OVERLAP_MAX_REFS) return WF_ERR_UNSUPPORTED;
-    if (!overlap_model_covered(m) || !overlap_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
+    if (!overlap_model_covered(m) || !measure_batch_covered(m, batch, false)) return WF_ERR_UNSUPPORTED;
     return overlap_step_layout(m, batch, K).total;
 }
 
@@ -63,7 +55,7 @@ int wf_vqmc_overlap_step(const wf_model* m, const wf_model* const* refs, int32_t
     }
     for (int k = 0; k < K; ++k)
         if (!refs[k] || refs[k]->desc.n_dim != m->desc.n_dim || refs[k]->device != m->device || !refs[k]->params_set) return WF_ERR_INVALID;
-    if (!overlap_model_covered(m) || !overlap_batch_covered(m, batch, true)) return WF_ERR_UNSUPPORTED;
+    if (!overlap_model_covered(m) || !measure_batch_covered(m, batch, true)) return WF_ERR_UNSUPPORTED;
     if (!m->params_set || !workspace_dev) return WF_ERR_INVALID;
     const OverlapStepLayout l = overlap_step_layout(m, batch, K);
     if (workspace_bytes < l.total) return WF_ERR_INVALID;

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib
+from . import _accum, _lib
 
 MAX_WALKERS = 1 << 20
 RECORD = ("sum_w", "sum_w_e", "sum_w_e2", "accepted", "left_domain", "not_finite")
@@ -48,20 +48,10 @@ PROTOTYPES = {
     "wf_vqmc_dmc_step": (_i32, [_vp, _state, _u64, _i64, _vp, _i32, _f64, _i32, _f64] + _ws + [_vp]),
 }
 
-_bound = None
-
 
 def lib():
     """The handle of _lib.lib() with PROTOTYPES applied to it."""
-    global _bound
-    L = _lib.lib()
-    if _bound is not L:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            f = getattr(L, name)
-            f.restype = restype
-            f.argtypes = argtypes
-        _bound = L
-    return L
+    return _lib.bound(PROTOTYPES)
 
 
 # ---- the host's restatement of the random streams and of the comb
@@ -134,14 +124,7 @@ def _check_walkers(n):
 
 
 def _float_tensor(t, shape, what, device=None, dtype=None):
-    import torch
-    dtype = dtype or torch.float32
-    if not hasattr(t, "is_cuda") or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must be a torch tensor of shape {list(shape)}")
-    if t.dtype != dtype or not t.is_contiguous():
-        raise ValueError(f"{what} must be contiguous {str(dtype).replace('torch.', '')}, got {t.dtype}")
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise ValueError(f"{what} must be a cuda tensor on the device of the walkers: DMC has no CPU fallback")
+    _accum.check_float_tensor(t, shape, what, "DMC has no CPU fallback", device, " on the device of the walkers", dtype)
 
 
 def _check_state_arrays(x, psi, grad, e_loc=None):

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, dmc, observables
+from . import _accum, _lib, dmc, observables
 
 MAX_SLOTS = 16
 COUNTS = ("counted", "skipped", "outside_density", "outside_pair")
@@ -43,20 +43,10 @@ PROTOTYPES = {
     "wf_vqmc_dmc_fw_step": (_i32, [_vp, ctypes.POINTER(dmc.DmcState), _fw, _u64, _i64, _vp, _i32, _f64, _i32, _f64] + _ws + [_vp]),
 }
 
-_bound = None
-
 
 def lib():
     """The handle of _lib.lib() with PROTOTYPES applied to it."""
-    global _bound
-    L = _lib.lib()
-    if _bound is not L:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            f = getattr(L, name)
-            f.restype = restype
-            f.argtypes = argtypes
-        _bound = L
-    return L
+    return _lib.bound(PROTOTYPES)
 
 
 # ---- checks: all of them before the first launch, none needs a GPU
@@ -87,11 +77,7 @@ class ForwardWalk:
         import torch
         (self.n, self.D, self.n_slots, self.stride, self.n_density_bins, self.n_pair_bins, self.lo, self.hi,
          self.series_len) = _check_tracker(n_walkers, D, n_slots, stride, n_density_bins, n_pair_bins, lo, hi, series_len)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("a ForwardWalk lives on a cuda device: forward walking has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _accum.cuda_device(device, "a ForwardWalk", "forward walking has no CPU fallback")
         z, S = dict(device=self.device), self.n_slots
         self.snap = torch.zeros(S, self.n, self.D, dtype=torch.float32, **z)
         self.anc = torch.zeros(S, self.n, dtype=torch.int32, **z)

@@ -15,13 +15,14 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _accum, _lib
 
 SCALARS = ("e_loc", "t_lap", "t_grad", "v_en", "v_ee")
 MAX_DENSITY_BINS, MAX_PAIR_BINS = 512, 1024
 
 _vp, _i32, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 _ws = [_vp, _i64]    # (workspace_dev, workspace_bytes)
+_NO_CPU = "the observables have no CPU fallback"
 
 
 class ObserveAcc(ctypes.Structure):
@@ -38,20 +39,10 @@ PROTOTYPES = {
     "wf_vqmc_observe_step": (_i32, [_vp, ctypes.POINTER(ObserveAcc), _vp, ctypes.c_uint64, _i64, _vp, _i32, _i32, _vp, _i32, _vp] + _ws + [_vp]),
 }
 
-_bound = None
-
 
 def lib():
     """The handle of _lib.lib() with PROTOTYPES applied to it."""
-    global _bound
-    L = _lib.lib()
-    if _bound is not L:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            f = getattr(L, name)
-            f.restype = restype
-            f.argtypes = argtypes
-        _bound = L
-    return L
+    return _lib.bound(PROTOTYPES)
 
 
 # ---- checks: all of them before the first launch, none needs a GPU
@@ -71,21 +62,10 @@ def _check_geometry(D, n_density_bins, n_pair_bins, lo, hi):
 def _check_step(batch, n_dim, walkers, out_walkers, values):
     """The arguments of one measurement step (core.DeviceModel.observe_step): `walkers` (read) and `out_walkers` (written) are contiguous
     float32 cuda tensors [batch, n_dim] or None, at most one of them given; `values` is a contiguous float32 cuda tensor [batch, 5] or None."""
-    import torch
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"{batch} walkers per step: at least 1")
-    if walkers is not None and out_walkers is not None:
-        raise ValueError("walkers (the step reads them) and out_walkers (the step writes what it drew) exclude each other")
-    for what, t, width in (("walkers", walkers, int(n_dim)), ("out_walkers", out_walkers, int(n_dim)), ("values", values, len(SCALARS))):
-        if t is None:
-            continue
-        if not hasattr(t, "is_cuda") or t.dim() != 2 or tuple(t.shape) != (batch, width):
-            raise ValueError(f"{what} must be a torch tensor of shape [{batch}, {width}]")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{what} must be contiguous float32, got {t.dtype}")
-        if not t.is_cuda:
-            raise ValueError(f"{what} must be a cuda tensor: the observables have no CPU fallback")
+    _accum.check_step_walkers(batch, n_dim, walkers, out_walkers, _NO_CPU, (("values", values, (batch, len(SCALARS))),))
     return batch
 
 
@@ -125,17 +105,8 @@ class Totals:
         This is how ranks that measured with different seeds combine.  Every rank must hold the same geometry.  The two buffers are host
         tensors under gloo; under any other backend (nccl: RCCL reduces device tensors only) they are moved to the current cuda device,
         reduced there and copied back."""
-        import torch
-        import torch.distributed as dist
-        from .distributed import _all_reduce_sum
-        f = torch.from_numpy(self.sums.reshape(-1).copy())
-        i = torch.from_numpy(np.concatenate([self.counts, self.density.reshape(-1), self.pair]).astype(np.int64))
-        if dist.get_backend(group) != "gloo":
-            f, i = f.cuda(), i.cuda()
-        _all_reduce_sum(f, group)
-        _all_reduce_sum(i, group)
-        self.sums = f.cpu().numpy().reshape(len(SCALARS), 2).copy()
-        i = i.cpu().numpy()
+        f, i = _accum.all_reduce_totals(self.sums, np.concatenate([self.counts, self.density.reshape(-1), self.pair]), group)
+        self.sums = f.reshape(len(SCALARS), 2)
         nd = self.D * self.n_density_bins
         self.counts, self.density, self.pair = i[:4].copy(), i[4:4 + nd].reshape(self.D, self.n_density_bins).copy(), i[4 + nd:].copy()
         return self
@@ -202,11 +173,7 @@ class Accumulator:
         self.D, self.n_density_bins, self.n_pair_bins, self.lo, self.hi = _check_geometry(D, n_density_bins, n_pair_bins, lo, hi)
         if device is None:
             device = f"cuda:{model.device}" if model is not None else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("an Accumulator lives on a cuda device: the observables have no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _accum.cuda_device(device, "an Accumulator", _NO_CPU)
         self.sums = torch.zeros(len(SCALARS), 2, dtype=torch.float64, device=self.device)
         self.counts = torch.zeros(4, dtype=torch.int64, device=self.device)
         self.density = torch.zeros(self.D, self.n_density_bins, dtype=torch.int64, device=self.device)
@@ -225,16 +192,6 @@ class Accumulator:
                       self.density.cpu().numpy(), self.pair.cpu().numpy())
 
 
-def _float_matrix(t, B, width, what, device):
-    import torch
-    if not hasattr(t, "is_cuda") or tuple(t.shape) != ((B, width) if width else (B,)):
-        raise ValueError(f"{what} must be a torch tensor of shape {[B, width] if width else [B]}")
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"{what} must be contiguous float32, got {t.dtype}")
-    if not t.is_cuda or t.device != device:
-        raise ValueError(f"{what} must be a cuda tensor on the device of the walkers: the observables have no CPU fallback")
-
-
 def accumulate(x, psi, grad, hdiag, protons, acc=None, return_values=False, workspace=None):
     """wf_observe_accumulate on x [B, D], psi [B], grad [B, D], hdiag [B, D] (contiguous float32 cuda, as DeviceModel.psi_derivatives returns
     them) and 1-D proton positions: adds the batch to `acc` (an Accumulator, or None with return_values) and returns the per-walker values
@@ -249,7 +206,7 @@ def accumulate(x, psi, grad, hdiag, protons, acc=None, return_values=False, work
     if not x.is_cuda:
         raise ValueError("x must be a cuda tensor: the observables have no CPU fallback")
     for what, t, width in (("x", x, D), ("psi", psi, 0), ("grad", grad, D), ("hdiag", hdiag, D)):
-        _float_matrix(t, B, width, what, x.device)
+        _accum.check_float_tensor(t, (B, width) if width else (B,), what, _NO_CPU, x.device, " on the device of the walkers")
     if acc is None and not return_values:
         raise ValueError("nothing to do: neither an accumulator nor return_values")
     if acc is not None and (acc.D != D or acc.device != x.device):
@@ -289,23 +246,9 @@ def measure(model, protons, n_walkers, batch, seed, exact_sampler=True, acc=None
     if acc is None:
         acc = Accumulator(model.D, model=model)
     counter = torch.zeros(1, dtype=torch.int64, device=acc.device)
-    steps = -(-n_walkers // batch)
-    acc.st["ws"] = model._workspace(model.observe_step_workspace_bytes(batch), acc.device)   # allocated here, outside the capture
 
     def step():
         model.observe_step(acc, counter, seed, batch, protons, exact_sampler=exact_sampler)
-    launch = step
-    if use_graph:
-        from . import vqmc
-        kept = [t.clone() for t in (acc.sums, acc.counts, acc.density, acc.pair, counter)]
-
-        def warm_up():
-            # one step outside the capture (the derivative entry grows the model's scratch there, not inside); what it added is taken back
-            step()
-            for t, k in zip((acc.sums, acc.counts, acc.density, acc.pair, counter), kept):
-                t.copy_(k)
-        launch = vqmc.capture_step(model, step, warm_up, "hipGraph capture of the measurement step failed")
-    for _ in range(steps):
-        launch()
-    torch.cuda.synchronize(acc.device)
+    _accum.measure_loop(model, acc, step, -(-n_walkers // batch), model.observe_step_workspace_bytes(batch),
+                        (acc.sums, acc.counts, acc.density, acc.pair, counter), "measurement", use_graph)
     return acc.totals()

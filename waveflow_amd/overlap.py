@@ -20,13 +20,14 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _accum, _lib
+from ._accum import BLOCK, GRID_BLOCKS   # noqa: F401  (the capped grid of the accumulation kernel: public here since the overlaps were added)
 
 MAX_REFS = 8
-GRID_BLOCKS, BLOCK = 1024, 256   # the capped grid of the accumulation kernel (csrc/wf_observe.h)
 
 _vp, _i32, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 _ws = [_vp, _i64]    # (workspace_dev, workspace_bytes)
+_NO_CPU = "the overlaps have no CPU fallback"
 
 
 class OverlapAcc(ctypes.Structure):
@@ -44,20 +45,10 @@ PROTOTYPES = {
     "wf_vqmc_overlap_step": (_i32, [_vp, _vp, _i32, _acc, _vp, ctypes.c_uint64, _i64, _i32, _vp, _i32, _vp] + _ws + [_vp]),
 }
 
-_bound = None
-
 
 def lib():
     """The handle of _lib.lib() with PROTOTYPES applied to it."""
-    global _bound
-    L = _lib.lib()
-    if _bound is not L:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            f = getattr(L, name)
-            f.restype = restype
-            f.argtypes = argtypes
-        _bound = L
-    return L
+    return _lib.bound(PROTOTYPES)
 
 
 # ---- checks: all of them before the first launch, none needs a GPU
@@ -113,21 +104,10 @@ def _check_vector(t, B, what, device=None, cuda=True):
 def _check_step(batch, n_dim, K, walkers, out_walkers, ratios):
     """The arguments of one measurement step (core.DeviceModel.overlap_step): `walkers` (read) and `out_walkers` (written) are contiguous
     float32 cuda tensors [batch, n_dim] or None, at most one of them given; `ratios` is a contiguous float32 cuda tensor [K, batch] or None."""
-    import torch
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"{batch} walkers per step: at least 1")
-    if walkers is not None and out_walkers is not None:
-        raise ValueError("walkers (the step reads them) and out_walkers (the step writes what it drew) exclude each other")
-    for what, t, shape in (("walkers", walkers, (batch, int(n_dim))), ("out_walkers", out_walkers, (batch, int(n_dim))), ("ratios", ratios, (K, batch))):
-        if t is None:
-            continue
-        if not hasattr(t, "is_cuda") or t.dim() != 2 or tuple(t.shape) != shape:
-            raise ValueError(f"{what} must be a torch tensor of shape {list(shape)}")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{what} must be contiguous float32, got {t.dtype}")
-        if not t.is_cuda:
-            raise ValueError(f"{what} must be a cuda tensor: the overlaps have no CPU fallback")
+    _accum.check_step_walkers(batch, n_dim, walkers, out_walkers, _NO_CPU, (("ratios", ratios, (K, batch)),))
     return batch
 
 
@@ -156,17 +136,8 @@ class Totals:
     def all_reduce(self, group=None):
         """SUM over the ranks of `group`, in place: one all-reduce for the fp64 part, one for the int64 part (distributed._all_reduce_sum), as
         observables.Totals.all_reduce.  Every rank must hold the same K."""
-        import torch
-        import torch.distributed as dist
-        from .distributed import _all_reduce_sum
-        f = torch.from_numpy(self.sums.reshape(-1).copy())
-        i = torch.from_numpy(self.counts.astype(np.int64).copy())
-        if dist.get_backend(group) != "gloo":
-            f, i = f.cuda(), i.cuda()
-        _all_reduce_sum(f, group)
-        _all_reduce_sum(i, group)
-        self.sums = f.cpu().numpy().reshape(self.K, 2).copy()
-        self.counts = i.cpu().numpy().copy()
+        f, self.counts = _accum.all_reduce_totals(self.sums, self.counts, group)
+        self.sums = f.reshape(self.K, 2)
         return self
 
     def result(self):
@@ -190,11 +161,7 @@ class Accumulator:
     def __init__(self, K, device=None):
         import torch
         self.K = _check_K(K)
-        self.device = torch.device("cuda" if device is None else device)
-        if self.device.type != "cuda":
-            raise ValueError("an Accumulator lives on a cuda device: the overlaps have no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _accum.cuda_device("cuda" if device is None else device, "an Accumulator", _NO_CPU)
         self.sums = torch.zeros(self.K, 2, dtype=torch.float64, device=self.device)
         self.counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.c = OverlapAcc(self.sums.data_ptr(), self.counts.data_ptr())
@@ -269,31 +236,6 @@ def penalise(e_loc, ratios, acc, penalty, out=None):
 
 # ---- the two kernels restated on the host
 
-def _ordered_sum(v):
-    """The fp64 sum of v [B] in the order of the device (include/waveflow_overlap.h): lane sums in walker order over the grid-stride loop, the
-    shuffle tree of a wave, the four waves of a block in order, the blocks in order.  A skipped walker enters as 0."""
-    B = v.shape[0]
-    blocks = min(-(-B // BLOCK), GRID_BLOCKS)
-    stride = blocks * BLOCK
-    passes = -(-B // stride)
-    padded = np.zeros(passes * stride, np.float64)
-    padded[:B] = v
-    lanes = np.zeros(stride, np.float64)
-    for p in range(passes):
-        lanes = lanes + padded[p * stride:(p + 1) * stride]
-    w = lanes.reshape(blocks, BLOCK // 64, 64)
-    for half in (32, 16, 8, 4, 2, 1):
-        w = w[..., :half] + w[..., half:2 * half]
-    w = w[..., 0]
-    per_block = w[:, 0]
-    for k in range(1, BLOCK // 64):
-        per_block = per_block + w[:, k]
-    total = np.float64(0.0)
-    for b in range(blocks):
-        total = total + per_block[b]
-    return total
-
-
 def reference_accumulate(psi, refs, sums=None, counts=None):
     """The accumulation kernel in numpy on float32 psi [B] and refs [K, B] -> (ratios [K, B] float32, sums [K, 2] float64, counts [2]
     int64): fp32 per operation, the fp64 sums of the batch in the order of the device, added to `sums` / `counts` (zeros by default)."""
@@ -314,8 +256,8 @@ def reference_accumulate(psi, refs, sums=None, counts=None):
     if psi.shape[0] > 0:
         for k in range(K):
             r = np.where(ok, ratios[k], f32(0.0)).astype(f64)
-            sums[k, 0] += _ordered_sum(r)
-            sums[k, 1] += _ordered_sum(r * r)
+            sums[k, 0] += _accum.ordered_sum(r)
+            sums[k, 1] += _accum.ordered_sum(r * r)
     counts += np.array([ok.sum(), (~ok).sum()], dtype=np.int64)
     return ratios, sums, counts
 
@@ -363,25 +305,11 @@ def measure(model, ref_models, n_walkers, batch, seed, exact_sampler=True, use_g
     if acc is None:
         acc = Accumulator(K, f"cuda:{model.device}")
     counter = torch.zeros(1, dtype=torch.int64, device=acc.device)
-    steps = -(-n_walkers // batch)
-    acc.st["ws"] = model._workspace(model.overlap_step_workspace_bytes(batch, K), acc.device)   # allocated here, outside the capture
 
     def step():
         model.overlap_step(ref_models, acc, counter, seed, batch, exact_sampler=exact_sampler)
-    launch = step
-    if use_graph:
-        from . import vqmc
-        kept = [t.clone() for t in (acc.sums, acc.counts, counter)]
-
-        def warm_up():
-            # one step outside the capture (the psi entry grows each model's scratch there, not inside); what it added is taken back
-            step()
-            for t, k in zip((acc.sums, acc.counts, counter), kept):
-                t.copy_(k)
-        launch = vqmc.capture_step(model, step, warm_up, "hipGraph capture of the overlap step failed")
-    for _ in range(steps):
-        launch()
-    torch.cuda.synchronize(acc.device)
+    _accum.measure_loop(model, acc, step, -(-n_walkers // batch), model.overlap_step_workspace_bytes(batch, K), (acc.sums, acc.counts, counter),
+                        "overlap", use_graph)
     return acc.totals()
 
 

@@ -13,7 +13,7 @@ CPU fallback, and arguments are checked before anything is launched (ValueError)
 """
 import ctypes
 
-from . import _lib
+from . import _accum, _lib
 
 MAX_WALKERS = 4096   # wf_sr_solve: Tbar is 128 MiB there
 
@@ -64,8 +64,6 @@ CG_PROTOTYPES = {
 MAX_ROWS = 65536     # the row passes (wf_sr_matvec, wf_sr_apply, wf_sr_cg_solve)
 SOLVERS = ('cholesky', 'cg')
 
-_bound = None
-
 
 class NotPositiveDefinite(ArithmeticError):
     """The Cholesky factorisation of Tbar + lambda I met a pivot that is not positive; `pivot` is its 1-based index."""
@@ -95,16 +93,7 @@ class NotFinite(ArithmeticError):
 
 def lib():
     """The handle of _lib.lib() with PROTOTYPES, STEP_PROTOTYPES, SPRING_PROTOTYPES and CG_PROTOTYPES applied to it."""
-    global _bound
-    L = _lib.lib()
-    if _bound is not L:
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(STEP_PROTOTYPES.items()) + list(SPRING_PROTOTYPES.items()) + list(
-                CG_PROTOTYPES.items()):
-            f = getattr(L, name)
-            f.restype = restype
-            f.argtypes = argtypes
-        _bound = L
-    return L
+    return _lib.bound(PROTOTYPES, STEP_PROTOTYPES, SPRING_PROTOTYPES, CG_PROTOTYPES)
 
 
 # ---- checks: all of them before the first launch, none needs a GPU
@@ -121,22 +110,11 @@ def _check_damping(damping, relative_damping):
 def _check_step(batch, n_dim, damping, relative_damping, walkers, out_walkers):
     """The arguments of one device-side training step (core.DeviceModel.sr_step) -> (damping, relative_damping); `walkers` (read) and
     `out_walkers` (written) are contiguous float32 cuda tensors [batch, n_dim] or None, and at most one of them is given."""
-    import torch
     damping, relative_damping = _check_damping(damping, relative_damping)
     batch = int(batch)
     if batch < 1 or batch > MAX_WALKERS:
         raise ValueError(f"{batch} walkers per step: the B x B solve is built for 1 .. {MAX_WALKERS}")
-    if walkers is not None and out_walkers is not None:
-        raise ValueError("walkers (the step reads them) and out_walkers (the step writes what it drew) exclude each other")
-    for what, t in (("walkers", walkers), ("out_walkers", out_walkers)):
-        if t is None:
-            continue
-        if not hasattr(t, "is_cuda") or t.dim() != 2 or tuple(t.shape) != (batch, int(n_dim)):
-            raise ValueError(f"{what} must be a torch tensor of shape [{batch}, {int(n_dim)}]")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{what} must be contiguous float32, got {t.dtype}")
-        if not t.is_cuda:
-            raise ValueError(f"{what} must be a cuda tensor: stochastic reconfiguration has no CPU fallback")
+    _accum.check_step_walkers(batch, n_dim, walkers, out_walkers, "stochastic reconfiguration has no CPU fallback")
     return damping, relative_damping
 
 
